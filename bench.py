@@ -16,6 +16,8 @@ The default run (what the driver records) carries, next to the headline line of 
 (configs[1] / configs[2] in the reference's other `Sample` type, the Python API's default dtype) — each with its own ms_per_step, value and roofline; `cold_ms_per_step` (the W + K steps from idle clocks, measured before anything
 else has run); `roofline.peak_measured` (sgx_membench: copy / read / write rates of this very device, in-process); and a
 NumPy / pocketfft datapoint inside `cpu_baseline`.  `--no-legs` switches the extra legs off.
+`--dump-outputs DIR` writes what the headline's last timed step computed to DIR/<workload>.npy (a fixed seeded sample of its rows
+when the batch is over 60 MB), so that two builds can be compared output for output on the same synthetic inputs.
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL).  Utterances shard by rank with no data-path
 collective (weak scaling: every rank owns a full batch); `--gather sync|overlap` adds the all-gather that reassembles the
@@ -49,6 +51,19 @@ WORKLOADS = {  # name -> (kernel workload, utterances per GPU, BASELINE config i
     # MFCC-13 (Mel-80 dB(-80) -> DCT-II + lifter 22, src/mfcc.rs:224-316) fused into the Mel-dB launch
     "mfcc": ("mfcc", 256, 2),
 }
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: array bytes at most (the .npy headers fit in the rest of 64 MB)
+DUMP_SEED = 2026         # the rows sampled from an output too large to dump whole: the same in every run
+
+
+def dump_rows(n_rows: int, row_bytes: int) -> np.ndarray:
+    """The rows (utterances) of a batched output that `--dump-outputs` writes: all of them when they fit DUMP_BYTES, else a fixed
+    seeded sample of as many as fit, in ascending order."""
+    k = min(n_rows, max(1, DUMP_BYTES // row_bytes))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, k, replace=False))
 
 
 def cfg_signal(b: int) -> np.ndarray:
@@ -278,6 +293,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the ranks rendezvous over gloo and time an empty step — exercises the launcher, the barrier / "
                          "max-over-ranks timing and the JSON line (tests/test_bench_launcher.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed (rank 0's output) "
+                         "as DIR/<workload>.npy: the whole batch when it fits in 60 MB, else a fixed seeded sample of its rows "
+                         "(listed in the JSON line under dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -789,6 +808,12 @@ def main() -> int:
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
+    if args.dump_outputs and args.dry_run:
+        print("bench.py: --dump-outputs: a dry run computes nothing", file=sys.stderr)
+        return 2
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
         return spawn_ranks(args)
@@ -915,6 +940,12 @@ def main() -> int:
         gather_ms = e0.elapsed_time(e1) / 5
     fence()
     dt, ev_ms = timed_steps(torch, stream, step, args.steps, fence)  # the stream the kernels are launched on (torch's current stream)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote, copied on the device now (the legs below reuse or free the buffers), to the host at the end
+        last = outs[(args.steps - 1) % nsets]
+        rows = dump_rows(last.shape[0], last[0].numel() * last.element_size())
+        dump = (rows, last.index_select(0, torch.from_numpy(rows).to(dev)))
     if gathered is None and overlap is None:
         kernel_ms = ev_ms  # mean launch duration over the timed region itself
     dt = reduce_max(dt)
@@ -1024,6 +1055,13 @@ def main() -> int:
             line["workloads"] = mr
     if watchdog is not None:
         watchdog.cancel()
+    if dump is not None:
+        rows, sample = dump
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        path = os.path.join(args.dump_outputs, f"{args.workload}.npy")
+        np.save(path, sample.cpu().numpy())
+        line["dump_outputs"] = {"file": path, "shape": list(sample.shape), "dtype": str(sample.dtype).replace("torch.", ""),
+                                "rows": rows.tolist(), "of_rows": batch}
     emit()
     if world > 1 or rehearse:
         dist.barrier()
