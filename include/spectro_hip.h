@@ -62,7 +62,7 @@ enum { SGX_WIN_RECTANGULAR = 0, SGX_WIN_HANNING = 1, SGX_WIN_HAMMING = 2, SGX_WI
  * matrix build_loghz_matrix :2438-2508) reuses n_mels / f_min / f_max as n_bins / f_min / f_max.  Erb (ErbParams
  * src/erb.rs:27-92, frequency-domain gammatone bank ErbFilterbank::generate :266-335, applied as a DENSE
  * n_filters x (n_fft/2+1) product with the power spectrum :374-401) reuses them as n_filters / f_min / f_max. */
-enum { SGX_FREQ_LINEAR = 0, SGX_FREQ_MEL = 1, SGX_FREQ_LOGHZ = 2, SGX_FREQ_ERB = 3, SGX_FREQ_CHROMA = 4 };
+enum { SGX_FREQ_LINEAR = 0, SGX_FREQ_MEL = 1, SGX_FREQ_LOGHZ = 2, SGX_FREQ_ERB = 3, SGX_FREQ_CHROMA = 4, SGX_FREQ_CQT = 5 };
 /* Chroma (src/chroma.rs): chromagram() :470-505 = linear MAGNITUDE spectrogram -> dense 12 x (n_fft/2+1) pitch-class bank
  * (build_chroma_filterbank :262-345, bins inside [f_min, f_max], Gaussian over the circular semitone distance, rows
  * normalised to unit sum) applied with sequential accumulation (:378-392) -> per-frame normalisation over the 12 rows
@@ -117,6 +117,33 @@ typedef struct {
  * longer frames are SGX_BACKEND ("n_fft too large"). */
 sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out);
 void sgx_plan_destroy(sgx_plan *plan);
+
+/* ---- constant-Q plans: SpectrogramPlanner::cqt_plan (src/spectrogram.rs:1127-1145), MappingKind::Cqt (:1785-1806, :1882-1904).
+ * CqtParams (src/cqt.rs:17-165) flattened.  n_bins = bins_per_octave * n_octaves, f_k = f_min 2^(k / bins_per_octave).  Per bin
+ * the kernel is K_k[j] = w[j] e^(+i 2 pi f_k j / sr), j < L_k = min(max(round(q sr / f_k), 1), n_fft) (round: half away from zero),
+ * w = the symmetric window of length L_k; coefficients with |K| < sparsity_threshold * max|K| are zeroed; with `normalize` K is
+ * multiplied by 1 / sqrt(sum |K|^2) when that sum is > 0 (src/cqt.rs:317-436).  A frame (unwindowed, same framing and centring as
+ * the STFT) gives Y_k = sum_j T(Re K_k[j]) x[n_fft - L_k + j] + i sum_j T(-Im K_k[j]) x[n_fft - L_k + j] (src/cqt.rs:495-522);
+ * the output is |Y_k|^2 -> amp_scale as for the other mappings, [batch][n_bins][n_frames].  The STFT window has no effect. */
+typedef struct {
+    uint32_t bins_per_octave, n_octaves;  /* both >= 1 */
+    double f_min;                         /* finite and > 0 (NaN is refused, where the reference lets it through) */
+    double q_factor;                      /* finite and > 0; CqtParams::new's default is 1 / (2^(1/bins_per_octave) - 1) */
+    int32_t window_kind;                  /* SGX_WIN_* except SGX_WIN_CUSTOM (one custom window cannot have every length L_k) */
+    double window_param;                  /* Kaiser beta / Gaussian std in samples */
+    double sparsity_threshold;            /* values <= 0 (and NaN) disable the sparsity step */
+    int32_t normalize;
+} sgx_cqt_params;
+
+/* params->freq_scale must be SGX_FREQ_CQT (sgx_plan_create refuses it); every sgx_params check of sgx_plan_create applies, the
+ * mapping fields (n_mels, f_min, f_max, mel_norm, MFCC, ERB, chroma) are not read.  Refused: f_{n_bins-1} >= sr / 2 ("CQT maximum
+ * frequency must be below Nyquist frequency"), SGX_AMP_COMPLEX, n_mfcc > 0.  sgx_execute, sgx_execute_timed, sgx_output_shape,
+ * sgx_axes (frequencies f_k), sgx_reserve (forward) and sgx_shard_execute work as on a Mel plan; the FFT entry points (sgx_r2c,
+ * sgx_c2r, sgx_istft) and sgx_mel_weights return SGX_INVALID_INPUT. */
+sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out);
+/* The kernels as built (f64, before the cast to T), packed bin after bin: bin k's L_k values start at sum_{i<k} L_i.  Pass NULL
+ * arrays to query `total` (= sum L_k) only; `lengths` has n_bins entries.  Works on host-only plans. */
+sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im);
 
 /* StftPlan::frame_count (:1230-1250) + SpectrogramPlan::output_shape (:512-519) */
 sgx_status sgx_output_shape(const sgx_plan *plan, size_t n_samples, size_t *n_bins, size_t *n_frames);
@@ -285,7 +312,8 @@ const char *sgx_last_error(const sgx_plan *plan);
 const char *sgx_last_create_error(void);
 /* Name of the kernel variant the plan dispatches to: the shape-specific kernels "r32x16_f32", "r32x32_f32", "r64x32_f32", "d512_f64", "d32x16_f64",
  * "d32x32_f64", or "reg_radix", "lds_radix2", "two_factor_dft", "bluestein", "direct_dft", or — frame lengths past the on-chip kernels, every n_fft up
- * to 2^20 (powers of two 2^21) — "big_four_step" / "big_chirpz" (transforms through global memory) (a diagnostic: a call may step down this chain for
+ * to 2^20 (powers of two 2^21) — "big_four_step" / "big_chirpz" (transforms through global memory); CQT plans: "cqt_mfma_lds"
+ * (the frames' samples staged in LDS) or "cqt_mfma_global" (spans too large for LDS) (a diagnostic: a call may step down this chain for
  * shapes the plan's kernel does not take). */
 const char *sgx_kernel_name(const sgx_plan *plan);
 int32_t sgx_abi_version(void);

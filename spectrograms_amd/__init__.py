@@ -9,7 +9,8 @@ from ._ffi import DimensionMismatchError, FFTBackendError, InternalError, Invali
 from .fft2d import (C2cPlan, Fft2dPlan, Fft2dPlanner, bandpass_filter, convolve_fft, detect_edges_fft, fft2d, fftfreq, fftshift,
                     fftshift_1d, gaussian_kernel_2d, highpass_filter, ifft2d, ifftshift, ifftshift_1d, lowpass_filter,
                     magnitude_spectrum_2d, power_spectrum_2d, rfftfreq, sharpen_fft)
-from .functions import (clear_fft_plan_cache, compute_chromagram, compute_erb_db_spectrogram,
+from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db_spectrogram,
+                        compute_cqt_magnitude_spectrogram, compute_cqt_power_spectrogram, compute_erb_db_spectrogram,
                         compute_erb_magnitude_spectrogram, compute_erb_power_spectrogram, compute_fft, compute_irfft,
                         compute_istft, compute_linear_db_spectrogram, compute_linear_magnitude_spectrogram,
                         compute_linear_power_spectrogram, compute_loghz_db_spectrogram,
@@ -17,7 +18,7 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_erb_db
                         compute_magnitude_spectrum, compute_mel_db_spectrogram, compute_mel_magnitude_spectrogram,
                         compute_mel_power_spectrogram, compute_mfcc, compute_power_spectrum, compute_rfft, compute_stft,
                         fft_plan_cache_info)
-from .params import (ChromaNorm, ChromaParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
+from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
 
@@ -27,6 +28,7 @@ LinearPowerPlan = LinearMagnitudePlan = LinearDbPlan = Plan
 MelPowerPlan = MelMagnitudePlan = MelDbPlan = Plan
 ErbPowerPlan = ErbMagnitudePlan = ErbDbPlan = Plan
 LogHzPowerPlan = LogHzMagnitudePlan = LogHzDbPlan = Plan
+CqtPowerPlan = CqtMagnitudePlan = CqtDbPlan = Plan
 
 __all__ = [
     "SpectrogramError", "InvalidInputError", "DimensionMismatchError", "FFTBackendError", "InternalError",
@@ -44,4 +46,6 @@ __all__ = [
     "magnitude_spectrum_2d", "fftshift", "ifftshift", "fftfreq", "rfftfreq", "fftshift_1d", "ifftshift_1d",
     "LinearPowerPlan", "LinearMagnitudePlan", "LinearDbPlan", "MelPowerPlan", "MelMagnitudePlan", "MelDbPlan",
     "ErbPowerPlan", "ErbMagnitudePlan", "ErbDbPlan", "LogHzPowerPlan", "LogHzMagnitudePlan", "LogHzDbPlan",
+    "CqtParams", "compute_cqt_power_spectrogram", "compute_cqt_magnitude_spectrogram", "compute_cqt_db_spectrogram",
+    "CqtPowerPlan", "CqtMagnitudePlan", "CqtDbPlan",
 ]

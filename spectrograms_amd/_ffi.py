@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SGX_LIB_PATH") or os.path.join(_PKG, "libspectro_hip.
 
 SGX_OK, SGX_INVALID_INPUT, SGX_DIM_MISMATCH, SGX_BACKEND, SGX_INTERNAL = range(5)
 WIN_RECTANGULAR, WIN_HANNING, WIN_HAMMING, WIN_BLACKMAN, WIN_KAISER, WIN_GAUSSIAN, WIN_CUSTOM = range(7)
-FREQ_LINEAR, FREQ_MEL, FREQ_LOGHZ, FREQ_ERB, FREQ_CHROMA = 0, 1, 2, 3, 4
+FREQ_LINEAR, FREQ_MEL, FREQ_LOGHZ, FREQ_ERB, FREQ_CHROMA, FREQ_CQT = 0, 1, 2, 3, 4, 5
 MELNORM_NONE, MELNORM_SLANEY, MELNORM_L1, MELNORM_L2 = range(4)
 AMP_POWER, AMP_MAGNITUDE, AMP_DECIBELS, AMP_COMPLEX = range(4)
 F32, F64 = 0, 1
@@ -31,7 +31,7 @@ SYMBOLS = [
     "sgx_reserve", "sgx_plan_device", "sgx_last_dim_mismatch",
     "sgx_c2c_create", "sgx_c2c_destroy", "sgx_c2c_forward", "sgx_c2c_inverse", "sgx_c2c_last_error",
     "sgx_comm_unique_id", "sgx_comm_create", "sgx_comm_adopt", "sgx_comm_destroy", "sgx_comm_last_error", "sgx_gather", "sgx_shard_execute", "sgx_shard_execute_chunked",
-    "sgx_membench", "sgx_clock_probe",
+    "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels",
 ]
 
 
@@ -44,6 +44,13 @@ class SgxParams(C.Structure):
         ("floor_db", C.c_double), ("dtype", C.c_int32), ("device", C.c_int32),
         ("n_mfcc", C.c_uint32), ("mfcc_include_c0", C.c_int32), ("mfcc_lifter", C.c_uint32), ("erb_spacing", C.c_int32),
         ("chroma_tuning", C.c_double), ("chroma_norm", C.c_int32),
+    ]
+
+
+class SgxCqtParams(C.Structure):
+    _fields_ = [
+        ("bins_per_octave", C.c_uint32), ("n_octaves", C.c_uint32), ("f_min", C.c_double), ("q_factor", C.c_double),
+        ("window_kind", C.c_int32), ("window_param", C.c_double), ("sparsity_threshold", C.c_double), ("normalize", C.c_int32),
     ]
 
 
@@ -150,6 +157,8 @@ def lib() -> C.CDLL:
     L.sgx_membench.argtypes = [C.c_int32, sz, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     L.sgx_clock_probe.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
     L.sgx_clock_probe.restype = C.c_int32
+    L.sgx_plan_create_cqt.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
+    L.sgx_cqt_kernels.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 

@@ -345,7 +345,7 @@ sgx_status validate(const sgx_params &p, std::string &msg) {
         if (p.chroma_norm < SGX_CHROMA_NORM_NONE || p.chroma_norm > SGX_CHROMA_NORM_MAX) return bad("unknown chroma normalisation");
         if (p.amp_scale != SGX_AMP_MAGNITUDE || p.has_log_params || p.n_mfcc > 0)
             return bad("chromagram is computed from the magnitude spectrogram (amp_scale = magnitude, no LogParams, no MFCC)");
-    } else if (p.freq_scale != SGX_FREQ_LINEAR) {
+    } else if (p.freq_scale != SGX_FREQ_LINEAR && p.freq_scale != SGX_FREQ_CQT) {  // (CQT: the mapping's checks are cqt_validate's)
         return bad("unknown frequency scale");
     }
     if (p.amp_scale < SGX_AMP_POWER || p.amp_scale > SGX_AMP_COMPLEX) return bad("unknown amplitude scale");
@@ -368,6 +368,75 @@ size_t frame_count(const sgx_params &p, size_t n_samples) {  // StftPlan::frame_
     return (padded - p.n_fft) / p.hop_size + 1;
 }
 
+// ---- constant-Q kernels (CqtKernel::generate, src/cqt.rs:317-436), f64 -------------------------------------------------------
+// CqtParams::new / with_q_factor (:17-70, :112-165) and FrequencyMapping<Cqt>::new (src/spectrogram.rs:1785-1806)
+sgx_status cqt_validate(const sgx_params &p, const sgx_cqt_params &c, std::string &msg) {
+    auto bad = [&](const char *m) { msg = std::string("Invalid input: ") + m; return SGX_INVALID_INPUT; };
+    if (c.bins_per_octave == 0) return bad("bins_per_octave must be > 0");
+    if (c.n_octaves == 0) return bad("n_octaves must be > 0");
+    if (uint64_t(c.bins_per_octave) * c.n_octaves > 0xffffffffull) return bad("bins_per_octave * n_octaves is too large");
+    if (!(c.f_min > 0.0 && std::isfinite(c.f_min))) return bad("f_min must be finite and > 0");  // (NaN refused here, cqt.rs:56-60 lets it through)
+    if (!(c.q_factor > 0.0 && std::isfinite(c.q_factor))) return bad("q_factor must be finite and > 0");
+    if (c.window_kind < SGX_WIN_RECTANGULAR || c.window_kind > SGX_WIN_CUSTOM) return bad("unknown window type");
+    // make_window panics on a Custom window whose length is not the kernel's (src/spectrogram.rs:2219-2226): the L_k differ per bin
+    if (c.window_kind == SGX_WIN_CUSTOM) return bad("CQT kernels need a window of every kernel length: a custom window is not accepted");
+    if (p.amp_scale == SGX_AMP_COMPLEX) return bad("complex output is not available on a CQT plan");
+    if (p.n_mfcc > 0) return bad("MFCC requires a Mel / Decibels plan");
+    const unsigned nb = c.bins_per_octave * c.n_octaves;
+    const double f_max = c.f_min * std::exp2(double(nb - 1) / double(c.bins_per_octave));
+    if (f_max >= p.sample_rate_hz / 2.0) return bad("CQT maximum frequency must be below Nyquist frequency");
+    return SGX_OK;
+}
+
+void build_cqt_kernels(const sgx_params &p, const sgx_cqt_params &c, std::vector<uint32_t> &len, std::vector<double> &re,
+                       std::vector<double> &im, std::vector<double> &freqs) {
+    const unsigned nb = c.bins_per_octave * c.n_octaves;
+    const double sr = p.sample_rate_hz;
+    len.assign(nb, 0);
+    freqs.assign(nb, 0.0);
+    re.clear();
+    im.clear();
+    sgx_params wp = p;
+    wp.window_kind = c.window_kind;
+    wp.window_param = c.window_param;
+    std::vector<double> w;
+    for (unsigned k = 0; k < nb; ++k) {
+        const double f = c.f_min * std::exp2(double(k) / double(c.bins_per_octave));  // bin_frequency :143-146
+        size_t L = sat_usize(std::round(c.q_factor * sr / f));  // f64::round: half away from zero; `as usize` saturates
+        L = std::min<size_t>(std::max<size_t>(L, 1), p.n_fft);
+        wp.n_fft = unsigned(L);
+        build_window(wp, {}, w);  // make_window(window, L) — the symmetric forms
+        const size_t base = re.size();
+        re.resize(base + L);
+        im.resize(base + L);
+        double *kr = re.data() + base, *ki = im.data() + base;
+        for (size_t n = 0; n < L; ++n) {  // generate_kernel_bin :387-413
+            const double phase = 2.0 * kPi * f * (double(n) / sr);
+            kr[n] = std::cos(phase) * w[n];
+            ki[n] = std::sin(phase) * w[n];
+        }
+        if (c.sparsity_threshold > 0.0) {  // apply_sparsity_threshold :415-437 (f64::max skips a NaN norm)
+            double mx = 0.0;
+            for (size_t n = 0; n < L; ++n) mx = std::fmax(mx, std::hypot(kr[n], ki[n]));
+            if (mx != 0.0) {
+                const double thr = mx * c.sparsity_threshold;
+                for (size_t n = 0; n < L; ++n)
+                    if (std::hypot(kr[n], ki[n]) < thr) kr[n] = ki[n] = 0.0;
+            }
+        }
+        if (c.normalize) {  // normalize_kernel :439-448
+            double energy = 0.0;
+            for (size_t n = 0; n < L; ++n) energy += kr[n] * kr[n] + ki[n] * ki[n];
+            if (energy > 0.0) {
+                const double nf = 1.0 / std::sqrt(energy);
+                for (size_t n = 0; n < L; ++n) { kr[n] *= nf; ki[n] *= nf; }
+            }
+        }
+        len[k] = uint32_t(L);
+        freqs[k] = f;
+    }
+}
+
 template <typename T>
 sgx_status upload(sgx_plan *pl, void **dst, const std::vector<T> &src) {
     if (src.empty()) { *dst = nullptr; return SGX_OK; }
@@ -384,6 +453,59 @@ sgx_status upload_cast(sgx_plan *pl, void **dst, const std::vector<double> &src)
 }
 
 sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need);
+
+// Device layout of a CQT plan (sgx_internal.h CqtArgs, cqt.hip): bins in ascending order in groups of 8, group g a dense [L_g][16]
+// block of T (column 2c = Re K, 2c + 1 = -Im K of bin 8 g + c, right-aligned: block row j is frame tap n_fft - L_g + j, zero in
+// front of a shorter kernel and in the columns past the last bin), L_g = the group's longest kernel rounded up to 16 taps.  The
+// groups are dealt to the 4 waves of a workgroup longest first, each to the wave with the fewest taps so far.
+template <typename T>
+sgx_status cqt_device_tables(sgx_plan *pl) {
+    const unsigned nb = unsigned(pl->cqt_len.size()), ng = pl->cqt_groups;
+    std::vector<uint32_t> info(4 * size_t(ng) + kCqtWaves + 1 + ng, 0);
+    std::vector<size_t> start(nb + 1, 0);
+    for (unsigned k = 0; k < nb; ++k) start[k + 1] = start[k] + pl->cqt_len[k];
+    size_t rows = 0;
+    std::vector<uint32_t> lg(ng);
+    for (unsigned g = 0; g < ng; ++g) {
+        uint32_t m = 0;
+        for (unsigned k = 8 * g; k < std::min(nb, 8 * g + 8); ++k) m = std::max(m, pl->cqt_len[k]);
+        lg[g] = (m + 15u) & ~15u;
+        info[4 * g] = uint32_t(rows);
+        info[4 * g + 1] = lg[g];
+        info[4 * g + 2] = 8 * g;
+        rows += lg[g];
+        if (rows > (size_t(1) << 31) / 16) return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: CQT kernel tables too large");
+    }
+    std::vector<T> tab(rows * 16, T(0));
+    for (unsigned k = 0; k < nb; ++k) {
+        const unsigned g = k / 8, c = k % 8, L = pl->cqt_len[k];
+        T *blk = tab.data() + size_t(info[4 * g]) * 16;
+        for (unsigned j = 0; j < L; ++j) {
+            const size_t row = size_t(lg[g] - L + j);
+            blk[row * 16 + 2 * c] = T(pl->cqt_re[start[k] + j]);       // T::from_f64(k.re)
+            blk[row * 16 + 2 * c + 1] = T(-pl->cqt_im[start[k] + j]);  // T::from_f64(-k.im)
+        }
+    }
+    // longest-first onto the least loaded wave; each wave's groups stay in ascending order
+    std::vector<std::vector<uint32_t>> per(kCqtWaves);
+    std::vector<size_t> load(kCqtWaves, 0);
+    for (unsigned g = 0; g < ng; ++g) {  // (L_g is non-increasing in g: f_k grows with k)
+        const size_t w = size_t(std::min_element(load.begin(), load.end()) - load.begin());
+        per[w].push_back(g);
+        load[w] += lg[g];
+    }
+    uint32_t *wb = info.data() + 4 * size_t(ng), *order = wb + kCqtWaves + 1;
+    uint32_t pos = 0;
+    for (unsigned w = 0; w < kCqtWaves; ++w) {
+        wb[w] = pos;
+        for (uint32_t g : per[w]) order[pos++] = g;
+    }
+    wb[kCqtWaves] = pos;
+    sgx_status st;
+    if ((st = upload<T>(pl, &pl->d_cqt_tab, tab)) != SGX_OK) return st;
+    if ((st = upload<uint32_t>(pl, &pl->d_cqt_info, info)) != SGX_OK) return st;
+    return upload<uint32_t>(pl, &pl->d_cqt_len, pl->cqt_len);
+}
 
 // Band schedule of the tuned f32 kernel (n_fft 1024, and 512 in its two-frames-per-transform mode), built on the HOST at plan
 // creation — before the kernel kind is resolved, so that a bank without a schedule (rows that are not runs of bins, too many
@@ -1005,8 +1127,41 @@ bool resolve_geometry(const sgx_plan *pl, StftArgs &a, KernelKind &kind) {
 }
 int chain_pos(KernelKind k) { return kind_is_tuned(k) ? 0 : k == K_REG_RADIX ? 1 : k == K_DIRECT_DFT ? 3 : 2; }  // (K_BLUESTEIN is chosen after the chain, at creation)
 
+sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out, size_t n_frames,
+                   hipStream_t s, int iters, float *ms) {
+    CqtArgs a{};
+    a.x = x;
+    a.out = out;
+    a.sample_stride = stride;
+    a.n_samples = n_samples;
+    a.batch = unsigned(batch);
+    a.n_fft = pl->p.n_fft;
+    a.hop = pl->p.hop_size;
+    a.pad = pl->p.centre ? pl->p.n_fft / 2 : 0;
+    a.n_frames = unsigned(n_frames);
+    a.n_bins = pl->n_out;
+    a.n_groups = pl->cqt_groups;
+    a.lpad = pl->cqt_lpad;
+    a.tab = pl->d_cqt_tab;
+    a.info = static_cast<const unsigned *>(pl->d_cqt_info);
+    a.len = static_cast<const unsigned *>(pl->d_cqt_len);
+    a.amp = pl->amp;
+    a.eps = pl->eps;
+    if (ms) SGX_HIP(pl, hipEventRecord(pl->ev0, s));
+    for (int i = 0; i < iters; ++i) SGX_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
+    if (ms) {
+        SGX_HIP(pl, hipEventRecord(pl->ev1, s));
+        SGX_HIP(pl, hipEventSynchronize(pl->ev1));
+        float t = 0.f;
+        SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
+        *ms = t / float(iters);
+    }
+    return SGX_OK;
+}
+
 sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out,
                       size_t n_frames, hipStream_t s, int iters, float *ms) {
+    if (pl->kind == K_CQT) return run_cqt(pl, x, batch, n_samples, stride, out, n_frames, s, iters, ms);
     StftArgs a;
     void *stage_out = out;
     bool mfcc = pl->p.n_mfcc > 0;
@@ -1082,7 +1237,7 @@ sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need) {
 
 void free_device(sgx_plan *pl) {
     void **bufs[] = {&pl->d_window, &pl->d_tw, &pl->d_tw1, &pl->d_tw2, &pl->d_mel_ptr, &pl->d_mel_col,
-                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_melbuf, &pl->d_pwbuf, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_itwr2, &pl->d_itw12, &pl->d_itwrd, &pl->d_itw1d, &pl->d_frames, &pl->d_flag, &pl->d_ones, &pl->d_in, &pl->d_out, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->bs_half.chirp, &pl->bs_half.bhp, &pl->bs_half.tw};
+                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_melbuf, &pl->d_pwbuf, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_itwr2, &pl->d_itw12, &pl->d_itwrd, &pl->d_itw1d, &pl->d_frames, &pl->d_flag, &pl->d_ones, &pl->d_in, &pl->d_out, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->bs_half.chirp, &pl->bs_half.bhp, &pl->bs_half.tw, &pl->d_cqt_tab, &pl->d_cqt_info, &pl->d_cqt_len};
     for (void **b : bufs)
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     big_free(pl->big);
@@ -1336,6 +1491,7 @@ const char *sgx_kernel_name(const sgx_plan *plan) {
     case K_REG_RADIX: return "reg_radix";
     case K_BLUESTEIN: return "bluestein";
     case K_BIGFFT: return plan->big_n & (plan->big_n - 1) ? "big_chirpz" : "big_four_step";
+    case K_CQT: return plan->cqt_m ? "cqt_mfma_lds" : "cqt_mfma_global";
     default: return "direct_dft";
     }
 }
@@ -1343,6 +1499,8 @@ const char *sgx_kernel_name(const sgx_plan *plan) {
 sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
     if (out) *out = nullptr;
     if (!params || !out) return create_fail(SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (params->freq_scale == SGX_FREQ_CQT)
+        return create_fail(SGX_INVALID_INPUT, "Invalid input: SGX_FREQ_CQT plans are created with sgx_plan_create_cqt (they need an sgx_cqt_params)");
     std::string msg;
     sgx_status st = validate(*params, msg);
     if (st != SGX_OK) return create_fail(st, msg);
@@ -1531,6 +1689,82 @@ sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
     return SGX_OK;
 }
 
+sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out) {
+    if (out) *out = nullptr;
+    if (!params || !cqt || !out) return create_fail(SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (params->freq_scale != SGX_FREQ_CQT)
+        return create_fail(SGX_INVALID_INPUT, "Invalid input: sgx_plan_create_cqt requires freq_scale = SGX_FREQ_CQT");
+    std::string msg;
+    sgx_status st = validate(*params, msg);  // StftPlan::new's checks first (spectrogram.rs:1136), then the mapping's
+    if (st != SGX_OK) return create_fail(st, msg);
+    if ((st = cqt_validate(*params, *cqt, msg)) != SGX_OK) return create_fail(st, msg);
+    if (params->n_fft > (1u << 15) && !big_supported(params->n_fft))  // (the same frame-length range as every other plan)
+        return create_fail(SGX_BACKEND, "hip -- FFT backend error: n_fft too large (the global-memory transforms take n_fft up to 2^20, powers of two up to 2^21)");
+    sgx_plan *pl = new (std::nothrow) sgx_plan();
+    if (!pl) return create_fail(SGX_INTERNAL, "Internal error: out of memory");
+    pl->p = *params;
+    if (params->window_kind == SGX_WIN_CUSTOM) pl->custom_window.assign(params->custom_window, params->custom_window + params->n_fft);
+    pl->p.custom_window = nullptr;
+    pl->dtype = params->dtype;
+    pl->elem = params->dtype == SGX_F64 ? 8 : 4;
+    pl->nb_fft = params->n_fft / 2 + 1;
+    pl->kind = K_CQT;
+    pl->out_mode = OUT_MEL;  // a mapping of the frame to n_bins rows
+    build_window(pl->p, pl->custom_window, pl->window);  // the STFT window (sgx_window); the CQT itself reads unwindowed frames
+    build_cqt_kernels(pl->p, *cqt, pl->cqt_len, pl->cqt_re, pl->cqt_im, pl->cqt_freqs);
+    pl->n_out = pl->n_final = unsigned(pl->cqt_len.size());
+    pl->p.n_mels = pl->n_out;
+    pl->amp = params->amp_scale == SGX_AMP_MAGNITUDE ? AMP_MAGNITUDE
+              : (params->amp_scale == SGX_AMP_DECIBELS && params->has_log_params) ? AMP_DB : AMP_POWER;  // S6
+    pl->eps = pl->amp == AMP_DB ? std::pow(10.0, params->floor_db / 10.0) : 0.0;
+    pl->cqt_groups = (pl->n_out + 7) / 8;
+    pl->cqt_lpad = (*std::max_element(pl->cqt_len.begin(), pl->cqt_len.end()) + 15u) & ~15u;
+    pl->cqt_m = cqt_lds_m(params->hop_size, pl->cqt_lpad, pl->dtype);
+    pl->device = params->device;
+    if (params->device != -2) {
+        int ndev = 0;
+        hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev <= 0) {
+            delete pl;
+            return create_fail(SGX_BACKEND, std::string("hip -- FFT backend error: no HIP device available (") + hipGetErrorString(e) + ")");
+        }
+        int dev = params->device;
+        if (dev == -1 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+        if (dev < 0 || dev >= ndev) {
+            delete pl;
+            return create_fail(SGX_INVALID_INPUT, "Invalid input: device ordinal out of range");
+        }
+        pl->device = dev;
+        DeviceGuard dg;
+        auto dev_init = [&]() -> sgx_status {
+            SGX_HIP(pl, dg.enter(dev));
+            SGX_HIP(pl, hipEventCreate(&pl->ev0));
+            SGX_HIP(pl, hipEventCreate(&pl->ev1));
+            return pl->dtype == SGX_F64 ? cqt_device_tables<double>(pl) : cqt_device_tables<float>(pl);
+        };
+        st = dev_init();
+        if (st != SGX_OK) {
+            g_create_err = pl->err;
+            free_device(pl);
+            delete pl;
+            return st;
+        }
+        pl->device_ready = true;
+    }
+    *out = pl;
+    return SGX_OK;
+}
+
+sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im) {
+    if (!plan) return SGX_INVALID_INPUT;
+    if (plan->kind != K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: plan is not a CQT plan");
+    if (total) *total = plan->cqt_re.size();
+    if (lengths) std::copy(plan->cqt_len.begin(), plan->cqt_len.end(), lengths);
+    if (re) std::copy(plan->cqt_re.begin(), plan->cqt_re.end(), re);
+    if (im) std::copy(plan->cqt_im.begin(), plan->cqt_im.end(), im);
+    return SGX_OK;
+}
+
 void sgx_plan_destroy(sgx_plan *plan) {
     if (!plan) return;
     if (plan->device_ready) {
@@ -1592,7 +1826,9 @@ sgx_status sgx_axes(const sgx_plan *plan, size_t n_frames, double *freqs, double
         const double dt = double(p.hop_size) / p.sample_rate_hz;
         for (size_t i = 0; i < n_frames; ++i) times[i] = double(i) * dt;
     }
-    if (freqs && plan->p.n_mfcc > 0) {  // Mfcc carries no frequency axis (src/mfcc.rs:130-133): report coefficient indices
+    if (freqs && plan->kind == K_CQT) {  // the kernels' centre frequencies (:1940-1943)
+        std::copy(plan->cqt_freqs.begin(), plan->cqt_freqs.end(), freqs);
+    } else if (freqs && plan->p.n_mfcc > 0) {  // Mfcc carries no frequency axis (src/mfcc.rs:130-133): report coefficient indices
         const unsigned skip = plan->p.n_mfcc - plan->n_final;
         for (unsigned i = 0; i < plan->n_final; ++i) freqs[i] = double(i + skip);
     } else if (freqs && p.freq_scale == SGX_FREQ_CHROMA) {  // pitch classes C..B carry no Hz axis: report their indices
@@ -1614,6 +1850,7 @@ sgx_status sgx_axes(const sgx_plan *plan, size_t n_frames, double *freqs, double
 
 sgx_status sgx_r2c(sgx_plan *plan, const void *in, size_t in_len, void *out, size_t out_len) {
     if (!plan) return SGX_INVALID_INPUT;
+    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
     if (!in || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
     const size_t n = plan->p.n_fft, nb = plan->nb_fft;
     if (in_len != n)  // validate_fft_io src/fft_backend.rs:264-282
@@ -1652,6 +1889,7 @@ sgx_status sgx_istft_length(const sgx_plan *plan, size_t n_frames, size_t *n_sam
 sgx_status sgx_istft(sgx_plan *plan, const void *stft, size_t batch, size_t n_bins, size_t n_frames, void *out,
                      size_t out_elems, int32_t mem_kind, void *hip_stream) {
     if (!plan) return SGX_INVALID_INPUT;
+    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
     if (!stft || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
     if (batch == 0 || n_frames == 0) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: stft matrix must be non-empty");
     if (n_bins != plan->nb_fft)  // :4876-4879
@@ -1679,6 +1917,7 @@ sgx_status sgx_istft(sgx_plan *plan, const void *stft, size_t batch, size_t n_bi
 
 sgx_status sgx_c2r(sgx_plan *plan, const void *in, size_t in_len, void *out, size_t out_len) {
     if (!plan) return SGX_INVALID_INPUT;
+    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
     if (!in || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
     const size_t n = plan->p.n_fft, nb = plan->nb_fft;
     if (in_len != nb)  // fft_backend.rs:538-544
@@ -1709,6 +1948,7 @@ sgx_status sgx_last_dim_mismatch(const sgx_plan *plan, size_t *expected, size_t 
 sgx_status sgx_reserve(sgx_plan *plan, size_t batch, size_t n_samples, int32_t host_staging, int32_t inverse) {
     if (!plan) return SGX_INVALID_INPUT;
     if (batch == 0 || n_samples == 0) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
+    if (inverse && plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
     if (!plan->device_ready)
         return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
     DeviceGuard dg;
@@ -1749,7 +1989,7 @@ sgx_status sgx_window(const sgx_plan *plan, double *out) {
 
 sgx_status sgx_mel_weights(const sgx_plan *plan, size_t *nnz, uint32_t *row_ptr, uint32_t *cols, double *vals) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->out_mode != OUT_MEL) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: plan has no Mel filterbank");
+    if (plan->out_mode != OUT_MEL || plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: plan has no Mel filterbank");
     if (nnz) *nnz = plan->mel_col.size();
     if (row_ptr) std::copy(plan->mel_ptr.begin(), plan->mel_ptr.end(), row_ptr);
     if (cols) std::copy(plan->mel_col.begin(), plan->mel_col.end(), cols);

@@ -19,7 +19,7 @@ namespace sgx {
 enum OutMode : int { OUT_LINEAR = 0, OUT_MEL = 1, OUT_COMPLEX = 2 };
 // AMP_MAG_IN: the mapping consumes sqrt(power) and its output is final (chromagram: bank applied to magnitudes)
 enum AmpMode : int { AMP_POWER = 0, AMP_MAGNITUDE = 1, AMP_DB = 2, AMP_MAG_IN = 3 };
-enum KernelKind : int { K_DIRECT_DFT = 0, K_LDS_RADIX2 = 1, K_R32X16_F32 = 2, K_TWO_FACTOR = 3, K_REG_RADIX = 4, K_BLUESTEIN = 5, K_R32X32_F32 = 6, K_D32X16_F64 = 7, K_D512_F64 = 8, K_R64X32_F32 = 9, K_D32X32_F64 = 10, K_BIGFFT = 11 };
+enum KernelKind : int { K_DIRECT_DFT = 0, K_LDS_RADIX2 = 1, K_R32X16_F32 = 2, K_TWO_FACTOR = 3, K_REG_RADIX = 4, K_BLUESTEIN = 5, K_R32X32_F32 = 6, K_D32X16_F64 = 7, K_D512_F64 = 8, K_R64X32_F32 = 9, K_D32X32_F64 = 10, K_BIGFFT = 11, K_CQT = 12 };
 inline bool kind_is_tuned(KernelKind k) { return k == K_R32X16_F32 || k == K_R32X32_F32 || k == K_D32X16_F64 || k == K_D512_F64 || k == K_R64X32_F32 || k == K_D32X32_F64; }  // the shape-specific kernels at the head of the chain
 
 // Kernel arguments (POD, passed by value).  Layouts in HBM:
@@ -265,6 +265,30 @@ hipError_t launch_big_stft(const BigDev &t, const StftArgs &a, void *scratch, in
 hipError_t launch_big_c2r(const BigDev &t, const C2rArgs &c, void *scratch, int dtype, hipStream_t s);     // Hermitian rows -> real rows [batch][nrows][ncols]
 hipError_t launch_big_c2c(const BigDev &t, const C2cArgs &c, void *scratch, int dtype, hipStream_t s);     // complex sequences (batch == 1)
 
+// ---- constant-Q plans (cqt.hip): the per-bin correlations as a GEMM on the matrix cores, rows = frames, K = taps, columns = groups
+// of 8 bins (16 columns: Re and -Im of each bin's kernel).  Group g is a dense [L_g][16] block of T, L_g = the group's longest
+// kernel rounded up to 16 taps, right-aligned at the frame's end (rows in front of a shorter bin's kernel are 0).
+//   info  : [n_groups] x {row offset of the block in `tab`, L_g, first bin, 0}, then wave_begin[kCqtWaves + 1], then the group
+//           order[n_groups]: wave w of a workgroup runs groups order[wave_begin[w] .. wave_begin[w + 1])
+//   len   : [n_bins] L_k (the exact recompute of frames with a non-finite sample in reach reads each bin's own L_k taps)
+constexpr unsigned kCqtWaves = 4;
+struct CqtArgs {
+    const void *x;
+    void *out;  // [batch][n_bins][n_frames] T
+    unsigned long long sample_stride, n_samples;
+    unsigned batch, n_fft, hop, pad, n_frames, n_bins, n_groups;
+    unsigned lpad;   // L_0 rounded up to 16: a frame's taps [n_fft - lpad, n_fft) are the only ones ever read
+    unsigned tiles;  // workgroup tiles per signal (16 m frames each)
+    const void *tab;
+    const unsigned *info;
+    const unsigned *len;
+    int amp;
+    double eps;
+};
+// frames per wave-row tile multiple m (4, 2, 1) whose sample span fits LDS, 0: none does (the A operands come from global memory)
+unsigned cqt_lds_m(unsigned hop, unsigned lpad, int dtype);
+hipError_t launch_cqt(const CqtArgs &a, unsigned lds_m, int dtype, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: remember which (kernel, device) pairs have been
 // configured, so a process that drives several GPUs (sgx_params.device) gets the large-LDS opt-in on each of them.
 inline hipError_t set_max_dynamic_lds(const void *fn, int bytes) {
@@ -392,6 +416,12 @@ struct sgx_plan {
     unsigned big_n = 0;  // set at creation when the plan's kind is K_BIGFFT (host-only plans have no tables)
     void *d_big = nullptr;
     size_t d_big_bytes = 0;
+
+    // K_CQT: kernels as built (f64, packed bin after bin), centre frequencies, the device layout (cqt.hip) and its LDS tiling
+    std::vector<uint32_t> cqt_len;
+    std::vector<double> cqt_re, cqt_im, cqt_freqs;
+    unsigned cqt_groups = 0, cqt_lpad = 0, cqt_m = 0;
+    void *d_cqt_tab = nullptr, *d_cqt_info = nullptr, *d_cqt_len = nullptr;
 
     // plan-owned staging for host-pointer execution
     void *d_in = nullptr, *d_out = nullptr;

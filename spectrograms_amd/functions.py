@@ -191,3 +191,16 @@ def compute_power_spectrum(samples, n_fft, window=None, dtype=None):
 def compute_magnitude_spectrum(samples, n_fft, window=None, dtype=None):
     """magnitude_spectrum (:4684-4693): sqrt of the power spectrum."""
     return _one_frame(samples, n_fft, window, _ffi.AMP_MAGNITUDE, dtype)
+
+
+def compute_cqt_power_spectrogram(samples, params, cqt, db=None, dtype=None):
+    """src/python/functions.rs:331-388 -> Spectrogram::<Cqt, Power, T>::compute."""
+    return Plan(params, _ffi.AMP_POWER, cqt, db, dtype).compute(samples)
+
+
+def compute_cqt_magnitude_spectrogram(samples, params, cqt, db=None, dtype=None):
+    return Plan(params, _ffi.AMP_MAGNITUDE, cqt, db, dtype).compute(samples)
+
+
+def compute_cqt_db_spectrogram(samples, params, cqt, db=None, dtype=None):
+    return Plan(params, _ffi.AMP_DECIBELS, cqt, db, dtype).compute(samples)

@@ -309,6 +309,99 @@ class MfccParams:
         return MfccParams(self.n_mfcc, self.include_c0, lifter)
 
 
+class CqtParams:
+    """CqtParams(bins_per_octave, n_octaves, f_min) — src/cqt.rs:17-165, Python class src/python/params.rs:1047-1098.
+
+    Defaults: q_factor = 1 / (2^(1/bins_per_octave) - 1), Hanning window, sparsity threshold 0.01, normalised kernels.  f_min must
+    be finite and > 0; a NaN f_min is refused too (the reference's check lets it through)."""
+
+    def __init__(self, bins_per_octave: int, n_octaves: int, f_min: float):
+        if int(bins_per_octave) <= 0 or int(n_octaves) <= 0:
+            raise ValueError("bins_per_octave and n_octaves must be > 0")  # NonZeroUsize
+        f_min = float(f_min)
+        if not (f_min > 0.0 and math.isfinite(f_min)):
+            raise _ffi.InvalidInputError("Invalid input: f_min must be finite and > 0")
+        self.bins_per_octave, self.n_octaves, self.f_min = int(bins_per_octave), int(n_octaves), f_min
+        self.q_factor = 1.0 / (2.0 ** (1.0 / self.bins_per_octave) - 1.0)
+        self.window = WindowType.hanning
+        self.sparsity_threshold = 0.01
+        self.normalize = True
+
+    @property
+    def num_bins(self) -> int:
+        return self.bins_per_octave * self.n_octaves
+
+    def bin_frequency(self, bin_idx: int) -> float:
+        return self.f_min * 2.0 ** (int(bin_idx) / self.bins_per_octave)
+
+    def bin_bandwidth(self, bin_idx: int) -> float:
+        return self.bin_frequency(bin_idx) / self.q_factor
+
+    def frequencies(self) -> list:
+        return [self.bin_frequency(i) for i in range(self.num_bins)]
+
+    def _copy(self) -> "CqtParams":
+        c = object.__new__(CqtParams)
+        c.__dict__.update(self.__dict__)
+        return c
+
+    def with_q_factor(self, q_factor: float) -> "CqtParams":
+        q_factor = float(q_factor)
+        if not (q_factor > 0.0 and math.isfinite(q_factor)):
+            raise _ffi.InvalidInputError("Invalid input: q_factor must be finite and > 0")
+        c = self._copy()
+        c.q_factor = q_factor
+        return c
+
+    def with_window(self, window: WindowType) -> "CqtParams":
+        c = self._copy()
+        c.window = window
+        return c
+
+    def with_sparsity(self, threshold: float) -> "CqtParams":
+        c = self._copy()
+        t = float(threshold)
+        c.sparsity_threshold = t if t > 0.0 else 0.0  # threshold.max(0.0): f64::max turns a NaN threshold into 0.0 too
+        return c
+
+    def with_normalize(self, normalize: bool) -> "CqtParams":
+        c = self._copy()
+        c.normalize = bool(normalize)
+        return c
+
+    @classmethod
+    def _preset(cls, bpo, n_oct, f_min, q=None, thr=0.01) -> "CqtParams":
+        c = cls(bpo, n_oct, f_min)
+        if q is not None:
+            c.q_factor = q
+        c.sparsity_threshold = thr
+        return c
+
+    # presets, cqt.rs:185-270
+    @classmethod
+    def percussive(cls) -> "CqtParams":
+        return cls._preset(12, 7, 32.7)
+
+    @classmethod
+    def onset_detection(cls) -> "CqtParams":
+        return cls._preset(24, 6, 55.0, 0.5, 0.02)
+
+    @classmethod
+    def chord_detection(cls) -> "CqtParams":
+        return cls._preset(36, 5, 82.4, 0.8, 0.02)
+
+    @classmethod
+    def harmonic(cls) -> "CqtParams":
+        return cls._preset(24, 7, 55.0, 1.0, 0.005)
+
+    @classmethod
+    def musical(cls) -> "CqtParams":
+        return cls._preset(12, 7, 32.7, 1.0, 0.01)
+
+    def __repr__(self):
+        return f"CqtParams(num_bins={self.num_bins})"
+
+
 def parse_dtype(dtype: Optional[str]) -> int:
     """src/python/dtype.rs:34-42."""
     d = "float64" if dtype is None else dtype

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _ffi
-from .params import ChromaParams, ErbParams, LogHzParams, LogParams, MelParams, MfccParams, SpectrogramParams, parse_dtype
+from .params import ChromaParams, CqtParams, ErbParams, LogHzParams, LogParams, MelParams, MfccParams, SpectrogramParams, parse_dtype
 
 
 class Spectrogram:
@@ -197,7 +197,12 @@ class Plan:
             p.custom_window = self._cw.ctypes.data_as(C.POINTER(C.c_double))
             p.custom_window_len = self._cw.size
         p.sample_rate_hz = params.sample_rate
-        if isinstance(mel, ChromaParams):
+        cq = None
+        if isinstance(mel, CqtParams):  # sgx_plan_create_cqt: the mapping's own parameters travel in sgx_cqt_params
+            p.freq_scale = _ffi.FREQ_CQT
+            cq = _ffi.SgxCqtParams(mel.bins_per_octave, mel.n_octaves, mel.f_min, mel.q_factor, mel.window.kind, mel.window.param,
+                                   mel.sparsity_threshold, int(mel.normalize))
+        elif isinstance(mel, ChromaParams):
             p.freq_scale = _ffi.FREQ_CHROMA
             p.f_min, p.f_max, p.chroma_tuning, p.chroma_norm = mel.f_min, mel.f_max, mel.tuning, mel.norm.code
         elif isinstance(mel, ErbParams):
@@ -220,7 +225,10 @@ class Plan:
         if mfcc is not None:
             p.n_mfcc, p.mfcc_include_c0, p.mfcc_lifter = mfcc.n_mfcc, int(mfcc.include_c0), mfcc.lifter
         h = C.c_void_p()
-        _ffi.raise_status(self._lib.sgx_plan_create(C.byref(p), C.byref(h)))
+        if cq is not None:
+            _ffi.raise_status(self._lib.sgx_plan_create_cqt(C.byref(p), C.byref(cq), C.byref(h)))
+        else:
+            _ffi.raise_status(self._lib.sgx_plan_create(C.byref(p), C.byref(h)))
         self._h = h
         self.n_fft = st.n_fft
         self._device = int(self._lib.sgx_plan_device(h))  # resolved ordinal (DEVICE_CURRENT was bound at creation); -2: host only
@@ -290,6 +298,19 @@ class Plan:
                                                     col.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                     val.ctypes.data_as(C.POINTER(C.c_double))), self._h)
         return ptr, col, val
+
+    def cqt_kernels(self):
+        """The CQT kernels as built (f64, before the cast to T; sgx_cqt_kernels): a list of n_bins complex arrays, bin k of length
+        L_k holding K_k[j] = w[j] e^(+i 2 pi f_k j / sr) after the sparsity step and the normalisation."""
+        total = C.c_size_t()
+        _ffi.raise_status(self._lib.sgx_cqt_kernels(self._h, C.byref(total), None, None, None), self._h)
+        lens = np.empty(self._mel.num_bins, np.uint32)
+        re, im = np.empty(total.value, np.float64), np.empty(total.value, np.float64)
+        _ffi.raise_status(self._lib.sgx_cqt_kernels(self._h, None, lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    re.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    im.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        cut = np.cumsum(lens.astype(np.int64))[:-1]
+        return [r + 1j * i for r, i in zip(np.split(re, cut), np.split(im, cut))]
 
     # ---- compute
     def _host_samples(self, samples, ndim: int) -> np.ndarray:
@@ -513,6 +534,15 @@ class SpectrogramPlanner:
         params = SpectrogramParams(stft_params, sample_rate)
         return Plan(params, _ffi.AMP_DECIBELS, MelParams(n_mels, 0.0, sample_rate / 2.0), LogParams(-80.0), dtype,
                     self._device, mfcc_params)
+
+    def cqt_power_plan(self, params, cqt_params, dtype=None):  # src/python/planner.rs:561-670
+        return Plan(params, _ffi.AMP_POWER, cqt_params, None, dtype, self._device)
+
+    def cqt_magnitude_plan(self, params, cqt_params, dtype=None):
+        return Plan(params, _ffi.AMP_MAGNITUDE, cqt_params, None, dtype, self._device)
+
+    def cqt_db_plan(self, params, cqt_params, db_params, dtype=None):
+        return Plan(params, _ffi.AMP_DECIBELS, cqt_params, db_params, dtype, self._device)
 
     def stft_plan(self, params, dtype=None):
         """StftPlan::new (src/spectrogram.rs:1204-1228)."""
