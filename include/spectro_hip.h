@@ -319,6 +319,36 @@ const char *sgx_kernel_name(const sgx_plan *plan);
 int32_t sgx_abi_version(void);
 int32_t sgx_device_count(void);
 
+/* ---- MDCT / IMDCT plans: MdctParams, mdct, imdct (src/mdct.rs:54-140, :387-497), batched.  window_size = 2N (even, >= 4), N
+ * coefficients per frame, any hop >= 1; the window is make_window(window_kind, 2N) (a custom window must have 2N coefficients: the
+ * reference panics there, this plan refuses it with SGX_INVALID_INPUT).  No centring and no padding: n_frames = (n_samples - 2N) / hop + 1,
+ * fewer than 2N samples are SGX_INVALID_INPUT ("samples length (..) must be >= window_size (..)").
+ *   forward  C[k, f] = sum_{n < 2N} x[f hop + n] w[n] cos(pi (2n + 1 + N)(2k + 1) / (4N)), k < N; out [batch][N][n_frames] T
+ *   inverse  y_f[m] = (2/N) sum_k C[k, f] cos(pi (2m + 1 + N)(2k + 1) / (4N)), m < 2N, times w[m], added in ascending frame order into a
+ *            zeroed [batch][hop n_frames + 2N - hop] T (no normalisation; zero frames: an empty output); n_coeffs != N is SGX_DIM_MISMATCH
+ * Supported: every even window_size up to 8192 and the powers of two up to 16384, both types (larger: SGX_BACKEND).  out_elems must be
+ * the exact element count (else SGX_DIM_MISMATCH); mem_kind and hip_stream as sgx_execute.  device -1: the current device, -2: a host-only
+ * plan (validation, shapes, window, routes; the compute calls return SGX_BACKEND). */
+typedef struct sgx_mdct sgx_mdct; /* opaque; same single-caller rule as sgx_fft2d / sgx_c2c */
+sgx_status sgx_mdct_create(size_t window_size, size_t hop_size, int32_t window_kind, double window_param, const double *custom_window,
+                           uint32_t custom_window_len, int32_t dtype, int32_t device, sgx_mdct **out);
+void sgx_mdct_destroy(sgx_mdct *plan);
+sgx_status sgx_mdct_output_shape(const sgx_mdct *plan, size_t n_samples, size_t *n_coeffs, size_t *n_frames);
+sgx_status sgx_mdct_inverse_length(const sgx_mdct *plan, size_t n_frames, size_t *n_samples);
+sgx_status sgx_mdct_forward(sgx_mdct *plan, const void *samples, size_t batch, size_t n_samples, void *out, size_t out_elems,
+                            int32_t mem_kind, void *hip_stream);
+sgx_status sgx_mdct_inverse(sgx_mdct *plan, const void *coeffs, size_t batch, size_t n_coeffs, size_t n_frames, void *out,
+                            size_t out_elems, int32_t mem_kind, void *hip_stream);
+/* Pre-sizes the plan-owned scratch (the generic route's chunk buffers; with host_staging the SGX_MEM_HOST staging) for forward calls of up
+ * to `batch` signals of `n_samples` samples and inverse calls of as many frames, so that those calls do not allocate. */
+sgx_status sgx_mdct_reserve(sgx_mdct *plan, size_t batch, size_t n_samples, int32_t host_staging);
+sgx_status sgx_mdct_window(const sgx_mdct *plan, double *out /* window_size values, f64 as built */);
+/* The route the plan runs in that direction: "k_mdct_fwd" (fused, N even with a register-tiled split of N/2), "k_imdct_ola" (fused, the
+ * same lengths at hop == N), else "mdct_generic" / "imdct_generic" (fold, batched complex transform, post-twiddle, overlap-add). */
+const char *sgx_mdct_kernel_name(const sgx_mdct *plan, int32_t inverse);
+int32_t sgx_mdct_device(const sgx_mdct *plan);
+const char *sgx_mdct_last_error(const sgx_mdct *plan); /* NULL plan: the text of the last failed create */
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db
                         compute_magnitude_spectrum, compute_mel_db_spectrogram, compute_mel_magnitude_spectrogram,
                         compute_mel_power_spectrogram, compute_mfcc, compute_power_spectrum, compute_rfft, compute_stft,
                         fft_plan_cache_info)
+from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
@@ -47,5 +48,5 @@ __all__ = [
     "LinearPowerPlan", "LinearMagnitudePlan", "LinearDbPlan", "MelPowerPlan", "MelMagnitudePlan", "MelDbPlan",
     "ErbPowerPlan", "ErbMagnitudePlan", "ErbDbPlan", "LogHzPowerPlan", "LogHzMagnitudePlan", "LogHzDbPlan",
     "CqtParams", "compute_cqt_power_spectrogram", "compute_cqt_magnitude_spectrogram", "compute_cqt_db_spectrogram",
-    "CqtPowerPlan", "CqtMagnitudePlan", "CqtDbPlan",
+    "CqtPowerPlan", "CqtMagnitudePlan", "CqtDbPlan", "MdctParams", "MdctPlan", "mdct", "imdct",
 ]

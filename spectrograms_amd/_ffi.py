@@ -32,6 +32,8 @@ SYMBOLS = [
     "sgx_c2c_create", "sgx_c2c_destroy", "sgx_c2c_forward", "sgx_c2c_inverse", "sgx_c2c_last_error",
     "sgx_comm_unique_id", "sgx_comm_create", "sgx_comm_adopt", "sgx_comm_destroy", "sgx_comm_last_error", "sgx_gather", "sgx_shard_execute", "sgx_shard_execute_chunked",
     "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels",
+    "sgx_mdct_create", "sgx_mdct_destroy", "sgx_mdct_output_shape", "sgx_mdct_inverse_length", "sgx_mdct_forward", "sgx_mdct_inverse",
+    "sgx_mdct_reserve", "sgx_mdct_window", "sgx_mdct_kernel_name", "sgx_mdct_device", "sgx_mdct_last_error",
 ]
 
 
@@ -159,6 +161,21 @@ def lib() -> C.CDLL:
     L.sgx_clock_probe.restype = C.c_int32
     L.sgx_plan_create_cqt.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
     L.sgx_cqt_kernels.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgx_mdct_create.argtypes = [sz, sz, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sgx_mdct_destroy.argtypes = [vp]
+    L.sgx_mdct_destroy.restype = None
+    L.sgx_mdct_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.sgx_mdct_inverse_length.argtypes = [vp, sz, C.POINTER(sz)]
+    L.sgx_mdct_forward.argtypes = [vp, vp, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_mdct_inverse.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_mdct_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_mdct_window.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_mdct_kernel_name.argtypes = [vp, C.c_int32]
+    L.sgx_mdct_kernel_name.restype = C.c_char_p
+    L.sgx_mdct_device.argtypes = [vp]
+    L.sgx_mdct_device.restype = C.c_int32
+    L.sgx_mdct_last_error.argtypes = [vp]
+    L.sgx_mdct_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -2007,3 +2007,7 @@ sgx_status sgx_shard_range(size_t batch, int32_t world_size, int32_t rank, size_
 }
 
 }  // extern "C"
+
+namespace sgx {
+void make_window_f64(const sgx_params &p, const std::vector<double> &custom, std::vector<double> &w) { build_window(p, custom, w); }
+}  // namespace sgx

@@ -289,6 +289,10 @@ struct CqtArgs {
 unsigned cqt_lds_m(unsigned hop, unsigned lpad, int dtype);
 hipError_t launch_cqt(const CqtArgs &a, unsigned lds_m, int dtype, hipStream_t s);
 
+// make_window (src/spectrogram.rs:2159-2235) in f64 at length p.n_fft for p.window_kind / p.window_param (plan.hip build_window);
+// SGX_WIN_CUSTOM copies `custom`.  The MDCT plans (mdct.hip) build their analysis / synthesis window with it.
+void make_window_f64(const sgx_params &p, const std::vector<double> &custom, std::vector<double> &w);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: remember which (kernel, device) pairs have been
 // configured, so a process that drives several GPUs (sgx_params.device) gets the large-LDS opt-in on each of them.
 inline hipError_t set_max_dynamic_lds(const void *fn, int bytes) {

@@ -58,8 +58,10 @@ def Plan(params, amp, mapping, db, dtype, mfcc=None, inverse=False):
 
 
 def clear_fft_plan_cache() -> None:
-    """Drop every cached plan (and its device tables)."""
+    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct included."""
+    from .mdct import clear_mdct_plan_cache
     _PLAN_CACHE.clear()
+    clear_mdct_plan_cache()
 
 
 def fft_plan_cache_info():
