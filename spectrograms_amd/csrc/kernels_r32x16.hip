@@ -690,6 +690,12 @@ __device__ __forceinline__ void mel_tile_sched(const StftArgs &a, const float *p
         SGX_STAMP(14);
 #endif
     }
+    if constexpr (TOLDS) {
+        // the chain's steps past the last band read +0, not what this half's FFT exchange left in the slot (another frame's data:
+        // 0 x NaN would carry one frame's NaN into the tile's clean frames)
+        for (unsigned i = a.n_mels * 16u + tid; i < 64u * (unsigned)TOLDS; i += 256u)
+            mfl[(((i >> 4) & 3u) * 16u + (i & 15u)) * (unsigned)TOLDS + (i >> 6)] = 0.0f;
+    }
 }
 
 // ---- fused MFCC epilogue (round 5; SURVEY.md §8 f1, src/mfcc.rs:224-316) ------------------------------------------------------------
@@ -702,8 +708,8 @@ __device__ __forceinline__ void mel_tile_sched(const StftArgs &a, const float *p
 //
 // Both operands sit in LDS with a lane's STEPS values contiguous — the band stage writes the tile's dB values as mq[q][n][s]
 // (mel_tile_sched<TOLDS>), the host lays the basis out as frag[mt][lane][s] — so a lane fetches them with STEPS / 2 16-byte reads (rows
-// of RL floats, RL / 4 odd: the 16 lanes of a read group on different banks).  Steps past the last band meet a zero weight and whatever
-// finite value the exchange left there.  One wave per half and 16 coefficients runs the chain (the f32 matrix instructions share the
+// of RL floats, RL / 4 odd: the 16 lanes of a read group on different banks).  Steps past the last band meet a zero weight and a +0
+// that mel_tile_sched writes there every tile (the exchange leaves other frames' data in those slots, non-finite ones included).  One wave per half and 16 coefficients runs the chain (the f32 matrix instructions share the
 // vector pipe: all eight waves running it redundantly, threaded through the next tile's pass 1, cost 12 us per 256 x 10 s for the chain and
 // 8 for its operand reads — profiles/experiments_r05/mfcc_fusion.md), at the top of the NEXT tile behind its barrier 1, where the registers are
 // still free and the barrier that publishes the band stage's writes is one the loop has anyway; the
