@@ -349,6 +349,59 @@ const char *sgx_mdct_kernel_name(const sgx_mdct *plan, int32_t inverse);
 int32_t sgx_mdct_device(const sgx_mdct *plan);
 const char *sgx_mdct_last_error(const sgx_mdct *plan); /* NULL plan: the text of the last failed create */
 
+/* ---- binaural plans: compute_{itd,ipd,ild,ilr}_spectrogram (src/binaural.rs:472-560, :830-900, :1187-1240, :1530-1600), batched over
+ * stereo pairs.  Each channel is the complex STFT (StftPlan::compute, src/spectrogram.rs:1424-1458) of the plan's STFT fields; with
+ * bw = sample_rate / n_fft, start_bin = round(start_freq / bw) and stop_bin = round(end_freq / bw) (f64, half away from zero), the map is
+ * [stop_bin - start_bin][n_frames] of, per bin k and frame (magphase :106-160 in T: mag = sqrt(fma(re, re, im im)), angle = atan2 of the
+ * unit phase, mag 0 and angle 0 where fma(re, re, im im) == 0):
+ *   ITD  pow(magL) + pow(magR) > 0 ? (np_mod(aL - aR + pi, 2 pi) - pi) / (2 pi bw k) : 0      (pow = magphase_power, :57-84)
+ *   IPD  wrapped ? np_mod(aL - aR + pi, 2 pi) - pi : aL - aR
+ *   ILD  magL + magR > 0 && magL > 0 && magR > 0 ? -20 log10(magR / magL) : NaN
+ *   ILR  same condition, r = magR / magL: r < 1 ? 1 - r : -(1 - 1 / r); else NaN
+ * with np_mod(x, m) = fmod(fmod(x, m) + m, m), in T. */
+enum { SGX_BINAURAL_ITD = 0, SGX_BINAURAL_IPD = 1, SGX_BINAURAL_ILD = 2, SGX_BINAURAL_ILR = 3 };
+typedef struct {
+    int32_t kind;             /* SGX_BINAURAL_* */
+    double start_freq;        /* Hz */
+    double end_freq;          /* Hz */
+    uint32_t magphase_power;  /* ITD: >= 1 (0 is SGX_INVALID_INPUT); read for validation only by the other kinds */
+    int32_t wrapped;          /* IPD: wrap the difference to [-pi, pi) */
+} sgx_binaural_params;
+typedef struct sgx_binaural sgx_binaural; /* opaque; same single-caller rule as sgx_plan */
+
+/* Only the STFT fields of `stft` are read (n_fft, hop_size, centre, window, sample_rate_hz, dtype, device); every sgx_plan_create check
+ * applies to them, device -2 gives a host-only plan (validation, shapes, axes, route).  Then, word for word as ITDSpectrogramParams::new
+ * (:410-460) and its siblings: "Start and end frequencies must be positive.", "Start frequency must be less than end frequency.", "End
+ * frequency must be less than Nyquist frequency." (end > sr / 2).  Refused where the reference panics or computes with nonsense: a NaN
+ * frequency ("Start and end frequencies must be finite."), magphase_power 0, an empty band stop_bin <= start_bin ("Frequency range should
+ * have at least one bin").  On failure *out is NULL and sgx_binaural_last_error(NULL) has the text. */
+sgx_status sgx_binaural_create(const sgx_params *stft, const sgx_binaural_params *params, sgx_binaural **out);
+void sgx_binaural_destroy(sgx_binaural *plan);
+/* start_bin, n_bins = stop_bin - start_bin, and the STFT's frame count for signals of n_samples samples */
+sgx_status sgx_binaural_output_shape(const sgx_binaural *plan, size_t n_samples, size_t *start_bin, size_t *n_bins, size_t *n_frames);
+/* frequencies bin * bw for the band's n_bins bins; times frame * hop / sample_rate (:541-553).  Either pointer may be NULL. */
+sgx_status sgx_binaural_axes(const sgx_binaural *plan, size_t n_frames, double *freqs, double *times);
+/* `batch` stereo pairs: left row r at left + r * sample_stride, right row r at right + r * sample_stride (elements of T), n_samples each;
+ * out [batch][n_bins][n_frames] T.  out_elems must be that count (else SGX_DIM_MISMATCH); mem_kind and hip_stream as sgx_execute. */
+sgx_status sgx_binaural_execute(sgx_binaural *plan, const void *left, const void *right, size_t batch, size_t n_samples, size_t sample_stride,
+                                void *out, size_t out_elems, int32_t mem_kind, void *hip_stream);
+/* The per-frame histograms of the Itd/Ipd/Ild/IlrSpectrogram::histogram methods (:323-370, :691-740, :1043-1090, :1385-1430) over maps
+ * `values` [batch][n_bins][n_frames] T as sgx_binaural_execute writes them: out [batch][num_bins][n_frames] f64.  A value counts 1 into
+ * bin min(floor((v - lo) / ((hi - lo) / num_bins)), num_bins - 1) (the cast saturates: NaN and negative quotients to 0) when it is finite
+ * and lo <= v <= hi; then, per cell, powi(exponent) when exponent != 1 (ILD / ILR; 1 for ITD / IPD), then with `normalize` each column is
+ * divided by its sum when that is > 0.  The counts are exact.  num_bins 1..32768. */
+sgx_status sgx_binaural_histogram(sgx_binaural *plan, const void *values, size_t batch, size_t n_frames, size_t num_bins, double lo, double hi,
+                                  int32_t exponent, int32_t normalize, double *out, size_t out_elems, int32_t mem_kind, void *hip_stream);
+/* Pre-sizes the plan-owned scratch (the spectra of a chunk of pairs; with host_staging the SGX_MEM_HOST staging of sgx_binaural_execute)
+ * for calls of up to `batch` pairs of `n_samples` samples, so that those calls do not allocate. */
+sgx_status sgx_binaural_reserve(sgx_binaural *plan, size_t batch, size_t n_samples, int32_t host_staging);
+/* The route: "r32x16_binaural_f32" (f32 n_fft 1024: both channels transformed and combined in one launch of the tuned kernel), else
+ * "binaural_epilogue/<complex STFT route>" (the plan's complex STFT on each channel into scratch, then the epilogue kernel,
+ * e.g. "binaural_epilogue/d32x16_f64"). */
+const char *sgx_binaural_kernel_name(const sgx_binaural *plan);
+int32_t sgx_binaural_device(const sgx_binaural *plan);
+const char *sgx_binaural_last_error(const sgx_binaural *plan); /* NULL plan: the text of the last failed create */
+
 #ifdef __cplusplus
 }
 #endif

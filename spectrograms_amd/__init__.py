@@ -6,6 +6,9 @@ include/spectro_hip.h.  There is no CPU fallback: if the library is not built, o
 compute calls raise FFTBackendError.
 """
 from ._ffi import DimensionMismatchError, FFTBackendError, InternalError, InvalidInputError, SpectrogramError
+from .binaural import (BinauralPlan, ILDSpectrogramParams, ILRSpectrogramParams, IPDSpectrogramParams, ITDSpectrogramParams,
+                       IldSpectrogram, IlrSpectrogram, IpdSpectrogram, ItdSpectrogram, compute_ild_spectrogram, compute_ilr_spectrogram,
+                       compute_ilr_spectrogram_diff, compute_ipd_spectrogram, compute_itd_spectrogram, compute_itd_spectrogram_diff)
 from .fft2d import (C2cPlan, Fft2dPlan, Fft2dPlanner, bandpass_filter, convolve_fft, detect_edges_fft, fft2d, fftfreq, fftshift,
                     fftshift_1d, gaussian_kernel_2d, highpass_filter, ifft2d, ifftshift, ifftshift_1d, lowpass_filter,
                     magnitude_spectrum_2d, power_spectrum_2d, rfftfreq, sharpen_fft)
@@ -49,4 +52,7 @@ __all__ = [
     "ErbPowerPlan", "ErbMagnitudePlan", "ErbDbPlan", "LogHzPowerPlan", "LogHzMagnitudePlan", "LogHzDbPlan",
     "CqtParams", "compute_cqt_power_spectrogram", "compute_cqt_magnitude_spectrogram", "compute_cqt_db_spectrogram",
     "CqtPowerPlan", "CqtMagnitudePlan", "CqtDbPlan", "MdctParams", "MdctPlan", "mdct", "imdct",
+    "ITDSpectrogramParams", "IPDSpectrogramParams", "ILDSpectrogramParams", "ILRSpectrogramParams", "ItdSpectrogram", "IpdSpectrogram",
+    "IldSpectrogram", "IlrSpectrogram", "BinauralPlan", "compute_itd_spectrogram", "compute_ipd_spectrogram", "compute_ild_spectrogram",
+    "compute_ilr_spectrogram", "compute_itd_spectrogram_diff", "compute_ilr_spectrogram_diff",
 ]

@@ -34,6 +34,8 @@ SYMBOLS = [
     "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels",
     "sgx_mdct_create", "sgx_mdct_destroy", "sgx_mdct_output_shape", "sgx_mdct_inverse_length", "sgx_mdct_forward", "sgx_mdct_inverse",
     "sgx_mdct_reserve", "sgx_mdct_window", "sgx_mdct_kernel_name", "sgx_mdct_device", "sgx_mdct_last_error",
+    "sgx_binaural_create", "sgx_binaural_destroy", "sgx_binaural_output_shape", "sgx_binaural_axes", "sgx_binaural_execute",
+    "sgx_binaural_histogram", "sgx_binaural_reserve", "sgx_binaural_kernel_name", "sgx_binaural_device", "sgx_binaural_last_error",
 ]
 
 
@@ -54,6 +56,14 @@ class SgxCqtParams(C.Structure):
         ("bins_per_octave", C.c_uint32), ("n_octaves", C.c_uint32), ("f_min", C.c_double), ("q_factor", C.c_double),
         ("window_kind", C.c_int32), ("window_param", C.c_double), ("sparsity_threshold", C.c_double), ("normalize", C.c_int32),
     ]
+
+
+BINAURAL_ITD, BINAURAL_IPD, BINAURAL_ILD, BINAURAL_ILR = range(4)
+
+
+class SgxBinauralParams(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("start_freq", C.c_double), ("end_freq", C.c_double), ("magphase_power", C.c_uint32),
+                ("wrapped", C.c_int32)]
 
 
 class SpectrogramError(Exception):
@@ -176,6 +186,20 @@ def lib() -> C.CDLL:
     L.sgx_mdct_device.restype = C.c_int32
     L.sgx_mdct_last_error.argtypes = [vp]
     L.sgx_mdct_last_error.restype = C.c_char_p
+    L.sgx_binaural_create.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxBinauralParams), C.POINTER(vp)]
+    L.sgx_binaural_destroy.argtypes = [vp]
+    L.sgx_binaural_destroy.restype = None
+    L.sgx_binaural_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.sgx_binaural_axes.argtypes = [vp, sz, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgx_binaural_execute.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_binaural_histogram.argtypes = [vp, vp, sz, sz, sz, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, sz, C.c_int32, vp]
+    L.sgx_binaural_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_binaural_kernel_name.argtypes = [vp]
+    L.sgx_binaural_kernel_name.restype = C.c_char_p
+    L.sgx_binaural_device.argtypes = [vp]
+    L.sgx_binaural_device.restype = C.c_int32
+    L.sgx_binaural_last_error.argtypes = [vp]
+    L.sgx_binaural_last_error.restype = C.c_char_p
     _lib = L
     return L
 

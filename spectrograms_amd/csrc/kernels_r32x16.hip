@@ -37,6 +37,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "binaural_kind.h"
 #include "buffer_ops.h"
 #include "fft_inreg.h"
 #include "r32x16_layout.h"
@@ -283,7 +284,7 @@ __device__ __forceinline__ void pass2_compute(v2f (&A)[16], v2f (&B)[16], bool j
         asm volatile("" ::: "memory");  // keeps this a branch (the compiler turned the selects into 48 v_cndmask per tile)
     }
     SGX_STAMP(9);  // 16-point transforms
-    constexpr int PSTEP = PWT ? 32 * 16 : 32;  // floats between bins k and k + 32 in the |X|^2 tile
+    constexpr int PSTEP = MODE == OUT_BINAURAL ? 32 * 16 * 2 : PWT ? 32 * 16 : 32;  // floats between bins k and k + 32 in the |X|^2 (binaural: X) tile
     auto emit = [&](unsigned voff, unsigned soff, float *pwp, v2f X, bool conj) {
 #ifdef SGX_ABL_NOSTORE  // timing experiment only: keep the value alive, drop the store
         asm volatile("" ::"v"(X), "v"(voff));
@@ -298,6 +299,8 @@ __device__ __forceinline__ void pass2_compute(v2f (&A)[16], v2f (&B)[16], bool j
             return;
 #endif
             *pwp = AMP == AMP_MAG_IN ? sqrtf(power_of(X)) : power_of(X);
+        } else if constexpr (MODE == OUT_BINAURAL) {  // the complex value to this half's spectrum tile (binaural_tile)
+            *(v2f *)pwp = conj ? (v2f){X.x, -X.y} : X;
         } else {
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, amp_f32<AMP>(power_of(X), eps)), ro, (int)voff, (int)soff, 0);
         }
@@ -798,6 +801,28 @@ __device__ __forceinline__ void mel_tile_sched512(const StftArgs &a, const float
     }
 }
 
+// ---- binaural maps (src/binaural.rs; binaural_kind.h) -------------------------------------------------------------------------------
+// After pass 2 each half has written its channel's X[k] of the tile's 16 frames to its own exchange buffer as spec[k][f] complex (513 x 16 x
+// 8 B = 65 664 B of the 65 792): half 0 the left channel, half 1 the right.  Behind one barrier the whole workgroup evaluates the kind
+// function over the band, lane (row r = i >> 4, frame f = i & 15), and stores each row's 16 frames as one 64-byte run.
+template <int KIND>
+__device__ __forceinline__ void binaural_tile(const StftArgs &a, const unsigned char *smem_all, unsigned b, unsigned f0, unsigned nf) {
+    binaural::KindConst<float> c;
+    c.pi = 3.14159265358979323846f;
+    c.two_pi = 2.0f * c.pi;
+    c.bw = (float)a.bin_bw;
+    c.power = a.bin_power;
+    c.wrapped = a.bin_wrapped;
+    const v2f *L = (const v2f *)smem_all, *R = (const v2f *)(smem_all + kExBytes);
+    float *out = (float *)a.out + ((size_t)b * a.bin_count) * a.n_frames + f0;
+    for (unsigned i = threadIdx.x; i < a.bin_count * 16u; i += 512u) {
+        const unsigned r = i >> 4, f = i & 15u, k = a.bin_start + r;
+        const v2f l = L[k * 16u + f], q = R[k * 16u + f];
+        const float v = binaural::binaural_value<float, KIND>(l.x, l.y, q.x, q.y, k, c);
+        if (f < nf) out[(size_t)r * a.n_frames + f] = v;
+    }
+}
+
 // ====================================================================================================================
 // k_r32x16: one persistent 512-thread workgroup per CU; its two halves each own a tile and an ex buffer and move through the
 // phases in lockstep (shared barriers) — measured 6-30 % faster than two independent 256-thread workgroups (round 1).
@@ -821,11 +846,17 @@ __device__ __forceinline__ void mel_tile_sched512(const StftArgs &a, const float
 // direct path, ROUNDS = 0) through one descriptor over the whole batch, each pair range-checked against its own row in the lane;
 // outputs through one descriptor from the tile's first signal.  The reference's per-frame loop costs the same per frame whatever
 // the signal length (src/spectrogram.rs:240-294).
+// MODE == OUT_BINAURAL (AMP = the SGX_BINAURAL_* kind; instances used by binaural plans only): the persistent walk hands ONE tile to both
+// halves — half 0 reads the left rows (a.x), half 1 the right rows (a.x2) — so each round covers one tile; passes 1 and 2 are unchanged,
+// pass 2 writes X to LDS (pass2_compute) and binaural_tile evaluates and stores the band.
 template <int MODE, int AMP, int ROUNDS, bool WIDE, bool XSPAD, bool PWT, int HOP512 = 0, bool PACK = false, int MSTEPS = 0>
 __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd, unsigned total, unsigned slots) {
     constexpr bool MFCC = MSTEPS != 0;  // fused MFCC epilogue, MSTEPS = ceil(n_mels / 4) rounded up to the menu (mfcc_tile)
     static_assert(!MFCC || (PWT && AMP == AMP_DB && HOP512 == 0 && !PACK), "fused MFCC epilogue: Mel-dB on the schedule, n_fft 1024, one-signal tiles");
     constexpr bool P512 = HOP512 != 0;           // n_fft 512 at hop HOP512
+    constexpr bool BIN = MODE == OUT_BINAURAL;
+    static_assert(!BIN || (!WIDE && !PWT && !P512 && !PACK && !MFCC), "binaural: one-signal n_fft 1024 tiles, per-half pass 2");
+    constexpr unsigned HS = BIN ? 1u : 2u;       // tiles per workgroup and round
     static_assert(!PACK || (ROUNDS == 0 && !WIDE && !XSPAD && (HOP512 == 0 ? (MODE != OUT_MEL || PWT) : MODE != OUT_MEL)),
                   "PACK: direct loads, one-half tiles; n_fft 1024: scheduled band stage, n_fft 512: per-bin outputs");
     constexpr unsigned SS512 = 8u * HOP512;      // bytes from one slot's (frame pair's) first sample to the next slot's
@@ -858,8 +889,8 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
     const unsigned xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
     const unsigned lo = xcd * per_xcd;
     const unsigned hi = min(lo + per_xcd, total);
-    unsigned wid = lo + slot * 2u + half;
-    unsigned lead = lo + slot * 2u;  // the first half's tile: uniform loop control for the whole workgroup
+    unsigned wid = lo + slot * HS + (BIN ? 0u : half);
+    unsigned lead = lo + slot * HS;  // the first half's tile: uniform loop control for the whole workgroup
 
     const unsigned p1f = tid >> 4, n2 = tid & 15u;  // pass-1 identity
     // pass-2 identity
@@ -886,7 +917,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
     auto load_tile = [&](unsigned w) {
         const unsigned b = w / a.tiles, tile = w - b * a.tiles;
         const unsigned f0 = tile * FPT;
-        const __amdgpu_buffer_rsrc_t rx = make_rsrc((const float *)a.x + (size_t)b * a.sample_stride, row_bytes);
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc((const float *)(BIN && half ? a.x2 : a.x) + (size_t)b * a.sample_stride, row_bytes);
         // first sample of the tile relative to the row; negative in the left padding: as an unsigned byte offset it is far out
         // of range, so the hardware returns 0 there as it does past the end of the row (S1: zero padding)
         const int tile_lo = (int)(f0 * hop) - (int)a.pad;
@@ -1118,12 +1149,12 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
 #endif
         twiddle_store(xr, twa, twb, smem + p1f * kFS + n2 * 8);
         SGX_STAMP(4);  // twiddles + ex writes
-        unsigned next = lead + slots * 2u + half;
-        if (next >= hi) next -= half;  // no tile of its own next round: repeat the first half's
+        unsigned next = lead + slots * HS + (BIN ? 0u : half);
+        if (next >= hi) next -= BIN ? 0u : half;  // no tile of its own next round: repeat the first half's
         // requested after pass 1 so the previous tile's store burst has had that long to drain: a vector load issued while
         // the CU's store FIFO is backed up stalls its wave for thousands of cycles
         if constexpr (!DMA)
-            if (lead + slots * 2u < hi) load_tile(next);  // in flight during pass 2
+            if (lead + slots * HS < hi) load_tile(next);  // in flight during pass 2
         SGX_STAMP(5);  // load issue
         __syncthreads();  // barrier 3: ex complete
         SGX_STAMP(6);
@@ -1169,7 +1200,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
         // DMA: the staging area (below the |X|^2 tile) is free from here on; the next tile's samples land in it during the real split
         // and the band stage (~5 k cycles: more than an HBM round trip)
         if constexpr (DMA)
-            if (lead + slots * 2u < hi) load_tile(next);
+            if (lead + slots * HS < hi) load_tile(next);
         float *pwf = (float *)(smem + (PWT ? POFF : 0u));  // PWT: above the staged samples, so the next staging does not wait for it
         if constexpr (MODE == OUT_MEL) {
             if constexpr (P512) {  // bins 257..267 are read with zero weights
@@ -1180,7 +1211,15 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
                 if (tid < 48u) pwf[(tid / 3u) * kPS + 513u + tid % 3u] = 0.0f;
             }
         }
-        if constexpr (P512 && PACK) {
+        if constexpr (BIN) {
+            const unsigned c1 = j == 0 ? 16u : j, c2 = j == 0 ? 0u : j + 256u;
+            auto slot_of = [&](unsigned k) { return (float *)smem + (k * 16u + p2f) * 2u; };  // spec[k][f], bins k + 32 i at i * PSTEP
+            pass2_compute<MODE, AMP, false>(A, B, j == 0, eps, twj, make_rsrc(a.out, 0u), 0u, 0u, 0u, 0u, 0u, 0u, slot_of(c1),
+                                            slot_of(512u - 224u - c1), slot_of(c2), slot_of(512u - 224u - c2), slot_of(256u) SGX_STAMP_ARGS);
+            __syncthreads();  // both channels' spectra complete
+            binaural_tile<AMP>(a, smem_all, b, f0, nf);
+            __syncthreads();  // spectra consumed: the next tile's staging / pass 1 may overwrite them
+        } else if constexpr (P512 && PACK) {
             constexpr unsigned kDrop = 0x80000000u;  // out of the descriptor's range: the store is dropped
             const __amdgpu_buffer_rsrc_t ro = make_rsrc((unsigned char *)a.out + (size_t)b * NB * a.n_frames * ES, min(17u, a.batch - b) * NB * a.n_frames * ES);
             const unsigned c1 = j == 0 ? 16u : j, r2 = j == 0 ? 0u : 32u - j;
@@ -1236,7 +1275,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
         }
         SGX_STAMP(14);  // filterbank stage
         wid = next;
-        lead += slots * 2u;
+        lead += slots * HS;
 #ifdef SGX_STAMPS
         st_acc[15] += 1;
 #endif
@@ -1351,6 +1390,24 @@ hipError_t launch_variant(const StftArgs &a0, hipStream_t s) {
     return go(k_r32x16<MODE, AMP, 0, W, false, false>);
 }
 
+template <int KIND>
+hipError_t launch_binaural(const StftArgs &a, hipStream_t s) {
+    const unsigned total = a.tiles * a.batch;  // one tile per workgroup and round
+    const unsigned per_xcd = (total + 7) / 8;
+    const unsigned chunks = (15u * a.hop + 1024u + 3u) >> 2;
+    const unsigned cu_slots = SGX_SLOTS ? SGX_SLOTS : std::max(1u, device_cu_count() / 8u);
+    const unsigned nslots = per_xcd < cu_slots ? per_xcd : cu_slots;
+    auto go = [&](auto kernel) -> hipError_t {
+        hipError_t e = set_max_dynamic_lds((const void *)kernel, 163840);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(nslots * 8), dim3(512), (unsigned)kLdsBytes, s, a, per_xcd, total, nslots);
+        return hipGetLastError();
+    };
+    if (a.hop == 256u) return go(k_r32x16<OUT_BINAURAL, KIND, 5, false, true, false>);
+    if (chunks <= 5u * 256u) return go(k_r32x16<OUT_BINAURAL, KIND, 5, false, false, false>);
+    return go(k_r32x16<OUT_BINAURAL, KIND, 0, false, false, false>);
+}
+
 }  // namespace
 
 #ifdef SGX_STAMPS
@@ -1387,6 +1444,18 @@ bool plan_geometry_r32x16_f32(StftArgs &a) {
     if ((unsigned long long)a.n_frames * 513ull * 8ull >= 0x7fffffffull) return false;  // and into a pair of output signals
     a.ft = 16;
     return true;
+}
+
+hipError_t launch_r32x16_binaural(const StftArgs &a, hipStream_t s) {
+    const unsigned long long total64 = (unsigned long long)a.tiles * a.batch;
+    if (a.n_fft != 1024u || a.out_mode != OUT_BINAURAL || total64 == 0 || total64 >= 0x7ffffff0ull || a.bin_start + a.bin_count > 513u)
+        return hipErrorInvalidConfiguration;
+    switch (a.amp) {
+    case SGX_BINAURAL_ITD: return launch_binaural<SGX_BINAURAL_ITD>(a, s);
+    case SGX_BINAURAL_IPD: return launch_binaural<SGX_BINAURAL_IPD>(a, s);
+    case SGX_BINAURAL_ILD: return launch_binaural<SGX_BINAURAL_ILD>(a, s);
+    default: return launch_binaural<SGX_BINAURAL_ILR>(a, s);
+    }
 }
 
 hipError_t launch_r32x16_f32(const StftArgs &a, hipStream_t s) {

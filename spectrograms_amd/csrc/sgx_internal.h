@@ -16,7 +16,7 @@
 
 namespace sgx {
 
-enum OutMode : int { OUT_LINEAR = 0, OUT_MEL = 1, OUT_COMPLEX = 2 };
+enum OutMode : int { OUT_LINEAR = 0, OUT_MEL = 1, OUT_COMPLEX = 2, OUT_BINAURAL = 3 };  // OUT_BINAURAL: k_r32x16 binaural instances only
 // AMP_MAG_IN: the mapping consumes sqrt(power) and its output is final (chromagram: bank applied to magnitudes)
 enum AmpMode : int { AMP_POWER = 0, AMP_MAGNITUDE = 1, AMP_DB = 2, AMP_MAG_IN = 3 };
 enum KernelKind : int { K_DIRECT_DFT = 0, K_LDS_RADIX2 = 1, K_R32X16_F32 = 2, K_TWO_FACTOR = 3, K_REG_RADIX = 4, K_BLUESTEIN = 5, K_R32X32_F32 = 6, K_D32X16_F64 = 7, K_D512_F64 = 8, K_R64X32_F32 = 9, K_D32X32_F64 = 10, K_BIGFFT = 11, K_CQT = 12 };
@@ -76,14 +76,31 @@ struct StftArgs {
     // fused MFCC epilogue of the tuned f32 kernel (kernels_r32x16.hip mfcc_tile; nullptr: separate launch_mfcc): the DCT-II basis as
     // v_mfma_f32_16x16x4_f32 A-fragments [mtiles][steps][64 lanes] = basis[16 mt + (l & 15)][4 s + (l >> 4)] (0 beyond n_mfcc / n_mels),
     // followed by the lifter weights [n_mfcc] (1.0 without a lifter); `out` then is the MFCC tensor [batch][n_mfcc - mfcc_skip][n_frames]
-    const void *mfcc_frag;
-    unsigned mfcc_frag_words, mfcc_steps, mfcc_mtiles, n_mfcc, mfcc_skip;
+    // The binaural route of the tuned f32 kernel (out_mode OUT_BINAURAL, amp = the SGX_BINAURAL_* kind; launch_r32x16_binaural) has no MFCC
+    // epilogue and shares these words with it (the layout, and with it every other instance's code, stays as it was): `x` holds the left
+    // rows, `x2` the right rows (same stride); `out` is [batch][bin_count][n_frames] for the bins bin_start .. bin_start + bin_count - 1;
+    // bin_bw = T::from_f64(sample_rate / n_fft).
+    union {
+        struct {
+            const void *mfcc_frag;
+            unsigned mfcc_frag_words, mfcc_steps, mfcc_mtiles, n_mfcc, mfcc_skip;
+        };
+        struct {
+            const void *x2;
+            unsigned bin_start, bin_count, bin_power;
+            int bin_wrapped;
+            float bin_bw;
+        };
+    };
 };
 
 // launchers (kernels_generic.hip / kernels_r32x16.hip); return hipSuccess or the launch error
 hipError_t launch_direct_dft(const StftArgs &a, int dtype, hipStream_t s);
 hipError_t launch_lds_radix2(const StftArgs &a, int dtype, hipStream_t s);
 hipError_t launch_r32x16_f32(const StftArgs &a, hipStream_t s);
+// binaural maps on the tuned f32 n_fft 1024 kernel: the two halves of a workgroup transform the left and the right tile of the same 16
+// frames and meet in LDS after pass 2 (kernels_r32x16.hip); a.tiles from plan_geometry_r32x16_f32
+hipError_t launch_r32x16_binaural(const StftArgs &a, hipStream_t s);
 hipError_t launch_r32x32_f32(const StftArgs &a, hipStream_t s);  // n_fft 2048 (kernels_r32x32.hip)
 bool plan_geometry_r32x32_f32(StftArgs &a);
 hipError_t launch_d32x16_f64(const StftArgs &a, hipStream_t s);  // f64 n_fft 1024, per-bin and complex outputs (kernels_d32x16.hip)
