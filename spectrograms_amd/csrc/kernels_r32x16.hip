@@ -5,11 +5,13 @@
 //   pass 1  lane (f = 0..15, n2 = 0..15) owns z[16*n1 + n2], n1 = 0..31, of frame f, where
 //           z[n] = w[2n] x[2n] + i w[2n+1] x[2n+1] is the half-length complex sequence of the real frame
 //           (window pre-scaled by 1/2 on the host — exact — so the real split needs no halving).
-//           Window multiply fused into the first butterflies; one 32-point FFT entirely in registers; twiddle by
-//           W_512^(k1*n2) from two short per-lane register tables; one ds_write_b64 per value.
+//           Window multiply fused into the first butterflies; one 32-point FFT entirely in registers; one ds_write_b64
+//           per value.  The twiddle W_512^(k1*n2) is applied in pass 2 (pass2_twiddle; n_fft 512 and the direct-load
+//           filterbank / binaural instances: here, from two short per-lane register tables).
 //   LDS     ex[f][k1][n2] complex f32, frame stride 4096+16 B.  This is the ONLY exchange of the transform.
 //   pass 2  lane (jq, f) owns "job" j of frame f: rows k1 = j and 32-j (job 0: rows 0 and 16).  8 + 8
-//           ds_read_b128 (conflict-free by the frame-stride / job-to-wave choice), two 16-point FFTs in registers
+//           ds_read_b128 (conflict-free by the frame-stride / job-to-wave choice), the rows' twiddles from one 15-entry
+//           per-lane table (row 32-j takes its conjugate and a one-bin rotation), two 16-point FFTs in registers
 //           -> Z[j+32*k2], Z[32-j+32*k2], and — because a job holds both members of every (k, 512-k) pair — the
 //           real split X[k] = E + W_1024^k O entirely in registers.
 //   store   the 16 lanes of a job hold the same bin of 16 consecutive frames, so out[b][k][f0..f0+15] is one
@@ -197,7 +199,26 @@ __device__ __forceinline__ void dma_rounds(__amdgpu_buffer_rsrc_t r, int voff, u
     }
 }
 
-// per-lane pass-1 twiddle tables: W_512^(k1*n2) = twa[k1>>3] * twb[k1&7]
+// x t and x conj(t) for a twiddle t held in registers, as v_pk_mul + ONE v_pk_fma_f32 whose operand modifiers form (-t.y, t.y) /
+// (t.y, -t.y): written in C, the compiler hoists the negated halves of a loop-invariant t into registers of their own (+15 VGPRs
+// for pass2_twiddle's table: spills) and negates a per-tile one with a v_xor_b32 of its own.  Same operations as cmulv.
+template <bool CONJ>
+__device__ __forceinline__ v2f cmul_reg(v2f x, v2f t) {
+    const v2f c = x * lo2(t);
+    v2f r;
+    if constexpr (CONJ) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(r) : "v"(x), "v"(t), "v"(c));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(x), "v"(t), "v"(c));
+    return r;
+}
+// D.x W' + D.y W'^perp with W'^perp = (-W'.y, W'.x): the real split's twiddle product, W' = w read from LDS (see cmul_reg)
+__device__ __forceinline__ v2f split_tw(v2f D, v2f w) {
+    const v2f c = lo2(D) * w;
+    v2f r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(D), "v"(w), "v"(c));
+    return r;
+}
+
+// per-lane pass-1 twiddle tables: W_512^(k1*n2) = twa[k1>>3] * twb[k1&7] (n_fft 512 instances; n_fft 1024 keeps only twa[2], see twiddle_store)
 __device__ __forceinline__ void load_tw1(const StftArgs &a, unsigned n2, v2f (&twa)[4], v2f (&twb)[8]) {
     const v2f *t1 = (const v2f *)a.tw1 + n2;
 #pragma unroll
@@ -206,14 +227,21 @@ __device__ __forceinline__ void load_tw1(const StftArgs &a, unsigned n2, v2f (&t
     for (int q = 0; q < 8; ++q) twb[q] = t1[16 * q];
 }
 
-// twiddle by W_512^(k1 n2) and write row k1 of this lane's column to ex
+// twiddle by W_512^(k1 n2) and write row k1 of this lane's column to ex.
+// P2 (n_fft 1024): the W_512 twiddles are applied in pass 2 by the lane that owns the row's job (pass2_twiddle): 60 packed instructions
+// there instead of 104 here.  Only row 0 is multiplied here, by conj(twa[2]) = W_32^(-n2): see pass2_twiddle.
+template <bool P2>
 __device__ __forceinline__ void twiddle_store(v2f (&xr)[32], const v2f (&twa)[4], const v2f (&twb)[8], unsigned char *dst) {
 #pragma unroll
     for (int k1 = 0; k1 < 32; ++k1) {
         const int qa = k1 >> 3, qb = k1 & 7;
         v2f r = xr[k1];
-        if (qb) r = cmulv(r, twb[qb]);
-        if (qa) r = cmulv(r, twa[qa]);
+        if constexpr (P2) {
+            if (k1 == 0) r = cmul_reg<true>(r, twa[2]);
+        } else {
+            if (qb) r = cmulv(r, twb[qb]);
+            if (qa) r = cmulv(r, twa[qa]);
+        }
 #if defined(SGX_ABL_NOEXW)  // timing experiments only (wrong results): the exchange not written at all — the upper bound of any cheaper exchange write
         asm volatile("" ::"v"(r), "v"(dst));
 #elif defined(SGX_ABL_ADDTID)  // ... or written as two ds_write_addtid_b32 per value (planar; 128 B/clk against ds_write_b64's ~85), M0 = the wave's 16 KiB
@@ -252,14 +280,28 @@ __device__ __forceinline__ JobOfs job_offsets(unsigned j, unsigned n_frames) {
     return JobOfs{c1 * n_frames, (512u - 224u - c1) * n_frames, c2 * n_frames, (512u - 224u - c2) * n_frames, 256u * n_frames};
 }
 
+// Pass-2 twiddles (n_fft 1024).  Row k1 of ex holds the pass-1 output before its twiddle W_512^(k1 n2).  A job owns rows j and 32 - j,
+// and W_512^((32 - j) n2) = W_16^n2 conj(W_512^(j n2)): with t[n2] = W_512^(j n2) (one per-lane table) row j is multiplied by t and
+// row 32 - j by conj(t), and the missing factor W_16^n2 only shifts the 16-point transform of row 32 - j by one bin: B[k2] then
+// holds Z[32 - j + 32 ((k2 - 1) & 15)] (pass2_compute reads it rotated).  Job 0 takes A = row 16 with t = W_512^(16 n2) and
+// B = row 0, which pass 1 multiplied by W_32^(-n2) = conj(t): with conj(t) here that makes W_16^(-n2), the same one-bin shift.
+__device__ __forceinline__ void pass2_twiddle(v2f (&A)[16], v2f (&B)[16], const v2f (&t)[16]) {
+#pragma unroll
+    for (int n = 1; n < 16; ++n) {
+        A[n] = cmul_reg<false>(A[n], t[n]);
+        B[n] = cmul_reg<true>(B[n], t[n]);
+    }
+}
+
 // pass 2 arithmetic + real split + output of one lane (job j of one frame).
-//   tw   : this job's 16 split twiddles in LDS, 16 bytes each = (W', W'^perp) with W' = -i W_1024^k (see plan.hip)
+//   A, B : rows j and 32 - j (job 0: 0 and 16) of ex; ROT: twiddled by pass2_twiddle (B read rotated), else twiddled in pass 1
+//   tw   : this job's 16 split twiddles in LDS, 8 bytes each = W' = -i W_1024^k (see plan.hip), two per 16-byte read
 //   out  : linear / complex: buffer descriptor + this lane's five byte offsets (frame included) + the scalar row step
 //   pw   : filterbank modes: this lane's |X|^2 slot bases (see PwAddr)
 struct PwAddr {
     float *up, *down;  // up[i * pstep] = bin c + 32 i; down[(7 - i) * pstep] = its mirror (both for c1 and, + c2off, for c2)
 };
-template <int MODE, int AMP, bool PWT>
+template <int MODE, int AMP, bool PWT, bool ROT>
 __device__ __forceinline__ void pass2_compute(v2f (&A)[16], v2f (&B)[16], bool j0, float eps, const v4f *tw, __amdgpu_buffer_rsrc_t ro,
                                               unsigned oa1, unsigned ob1, unsigned oa2, unsigned ob2, unsigned omid, unsigned step,
                                               float *pw_c1, float *pw_m1, float *pw_c2, float *pw_m2, float *pw_mid SGX_STAMP_PARAMS) {
@@ -267,20 +309,36 @@ __device__ __forceinline__ void pass2_compute(v2f (&A)[16], v2f (&B)[16], bool j
     // pairing below: first loop (A[i], B[15-i]), second loop (A[8+t], B[7-t]).
     //   first  loop wants (B[i], B[15-i])            -> A'[i] = B[i], B'[8..15] unchanged
     //   second loop wants (A[t], A[(16-t) & 15])     -> A'[8+t] = A[t], B'[7-t] = A[(16-t) & 15]
+    //   ROT: B is read rotated, B[(m + 1) & 15] is the value the pairing below calls B[m] (pass2_twiddle); job 0 holds rows 16 and 0
+    constexpr int R = ROT ? 1 : 0;
     Fft<16, false>::run(A, A);
     Fft<16, false>::run(B, B);
-    const v2f a8 = A[8];
+    const v2f a8 = ROT ? B[9] : A[8];  // Z[256]: row 0, k2 = 8
     if (j0) {
-        v2f nA[16], nB[8];
+        if constexpr (ROT) {  // A = row 16 (in place for the first loop), B = row 0 rotated
+            v2f nA[8], nB[16];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { nA[i] = B[i]; nA[8 + i] = A[i]; }
-        nB[7] = A[0];
+            for (int t = 0; t < 8; ++t) nA[t] = B[t + 1];  // second loop: A[8 + t] = Z[32 t]
 #pragma unroll
-        for (int t = 1; t < 8; ++t) nB[7 - t] = A[16 - t];
+            for (int i = 0; i < 8; ++i) nB[(16 - i) & 15] = A[15 - i];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) A[i] = nA[i];
+            for (int t = 0; t < 8; ++t) nB[8 - t] = B[(17 - t) & 15];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) B[i] = nB[i];
+            for (int t = 0; t < 8; ++t) A[8 + t] = nA[t];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) B[i] = nB[i];
+        } else {
+            v2f nA[16], nB[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { nA[i] = B[i]; nA[8 + i] = A[i]; }
+            nB[7] = A[0];
+#pragma unroll
+            for (int t = 1; t < 8; ++t) nB[7 - t] = A[16 - t];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) A[i] = nA[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) B[i] = nB[i];
+        }
         asm volatile("" ::: "memory");  // keeps this a branch (the compiler turned the selects into 48 v_cndmask per tile)
     }
     SGX_STAMP(9);  // 16-point transforms
@@ -306,25 +364,29 @@ __device__ __forceinline__ void pass2_compute(v2f (&A)[16], v2f (&B)[16], bool j
         }
     };
     // pair (P, Q) = (Z[k], Z[512-k]):  E = (P.x+Q.x, P.y-Q.y), D = (P.x-Q.x, P.y+Q.y), O = -i D, T = W O = W' D with W' = -i W:
-    //   T = D.x W' + D.y W'^perp;  X[k] = E + T, X[512-k] = conj(E - T)
-    auto split = [&](v2f P, v2f Q, v4f w, v2f &X, v2f &Y) {
+    //   T = D.x W' + D.y W'^perp, W'^perp = (-W'.y, W'.x) (operand modifiers);  X[k] = E + T, X[512-k] = conj(E - T)
+    auto twi = [&](int i) {
+        const v4f q = tw[i >> 1];
+        return (i & 1) ? (v2f){q.z, q.w} : (v2f){q.x, q.y};
+    };
+    auto split = [&](v2f P, v2f Q, v2f w, v2f &X, v2f &Y) {
         const v2f E = pfma(Q, (v2f){1.f, -1.f}, P);
         const v2f D = pfma(Q, (v2f){-1.f, 1.f}, P);
-        const v2f T = pfma(hi2(D), (v2f){w.z, w.w}, lo2(D) * (v2f){w.x, w.y});
+        const v2f T = split_tw(D, w);
         X = E + T;
         Y = E - T;
     };
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         v2f X, Y;
-        split(A[i], B[15 - i], tw[i], X, Y);
+        split(A[i], B[(15 + R - i) & 15], twi(i), X, Y);
         emit(oa1, i * step, pw_c1 + i * PSTEP, X, false);
         emit(ob1, (7 - i) * step, pw_m1 + (7 - i) * PSTEP, Y, true);
     }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         v2f X, Y;
-        split(A[8 + t], B[7 - t], tw[8 + t], X, Y);
+        split(A[8 + t], B[7 + R - t], twi(8 + t), X, Y);
         emit(oa2, t * step, pw_c2 + t * PSTEP, X, false);
         emit(ob2, (7 - t) * step, pw_m2 + (7 - t) * PSTEP, Y, true);
     }
@@ -875,7 +937,13 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
     unsigned char *smem = smem_all + half * EXB;  // this half's ex / xs / pw buffer
     unsigned char *tabs = smem_all + 2 * EXB;     // tables sit behind the two ex buffers
     if (threadIdx.x < 256u) ((v4f *)(tabs + kWinOff))[threadIdx.x] = ((const v4f *)a.window)[threadIdx.x];
-    for (unsigned i = threadIdx.x; i < 16u * 17u; i += 512u) ((v4f *)(tabs + kTw2Off))[i] = ((const v4f *)a.tw2)[i];
+    if (threadIdx.x < 256u) {  // split twiddles: W' of entry i of job j (the first half of the host's (W', W'^perp)), jobs kTw2Stride bytes apart
+        const unsigned jj = threadIdx.x >> 4, ii = threadIdx.x & 15u;
+        const v4f q = ((const v4f *)a.tw2)[jj * 17u + ii];
+        *(v2f *)(tabs + kTw2Off + jj * kTw2Stride + ii * 8u) = (v2f){q.x, q.y};
+        // (TRLDS) the pass-2 row twiddles W_512^(r n) of job jj, r = its first row (job 0: 16)
+        *(v2f *)(tabs + kTrOff + jj * 128u + ii * 8u) = ((const v2f *)a.tw1)[(jj == 0u ? 16u : jj) * 16u + ii];
+    }
     unsigned *sched = (unsigned *)(tabs + kMelOff);
     if constexpr (PWT)
         for (unsigned i = threadIdx.x; i < a.mel_sched_words; i += 512u) sched[i] = a.mel_sched[i];
@@ -898,14 +966,28 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
     const unsigned wv_ = WIDE ? threadIdx.x >> 6 : tid >> 6;
     const unsigned jq = WIDE ? lane >> 5 : lane >> 4, p2f = WIDE ? lane & 31u : lane & 15u;
     const unsigned j = wv_ + (WIDE ? 8u : 4u) * jq;
-    const unsigned ra = j, rb = j == 0 ? 16u : 32u - j;
+    // TWP2 (the n_fft 1024 per-bin and binaural instances — all of them, since PACK / B = 1 / binaural / complex results are compared bit
+    // for bit across instances): the W_512 twiddles of pass 1 are applied in pass 2 (pass2_twiddle) — 42 fewer packed instructions per
+    // lane and tile.  Job 0 then holds rows 16 and 0.  tr, 30 VGPRs, lives in registers; TRLDS (the direct-load instances, which hold
+    // 32 sample pairs in registers and would spill) reads it from LDS per tile instead (kTrOff: 128 bytes per job).  The filterbank
+    // instances keep the pass-1 twiddles: with them Mel-80 power measured 112.5 -> 118.3 us (profiles/r06_linear_isa_budget.md).
+    constexpr bool TWP2 = !P512 && MODE != OUT_MEL;
+    constexpr bool TRLDS = TWP2 && ROUNDS == 0 && !WIDE;
+    const unsigned ra = j == 0 ? (TWP2 ? 16u : 0u) : j, rb = j == 0 ? (TWP2 ? 0u : 16u) : 32u - j;
     const float eps = (float)a.eps;
     constexpr unsigned ES = MODE == OUT_COMPLEX ? 8u : 4u;
     const JobOfs jo = job_offsets(j, a.n_frames);
     const unsigned step = 32u * a.n_frames * ES;  // uniform: 32 bins further
-    const v4f *twj = (const v4f *)(tabs + kTw2Off) + j * 17u;
-    v2f twa[4], twb[8];
-    load_tw1(a, n2, twa, twb);
+    const v4f *twj = (const v4f *)(tabs + kTw2Off + j * kTw2Stride);
+    v2f twa[4], twb[8], tr[16];
+    if constexpr (!TWP2) {
+        load_tw1(a, n2, twa, twb);
+    } else {  // tr[n2] = W_512^(ra n2), the pass-2 twiddles of this lane's job; twa[2] = W_512^(16 n2) for row 0 in pass 1
+        twa[2] = ((const v2f *)a.tw1)[16 * 16 + n2];
+        if constexpr (!TRLDS)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) tr[q] = ((const v2f *)a.tw1)[ra * 16u + q];
+    }
 
     // staged path: this thread's 16-byte chunks of the tile being prefetched; direct path: its column
     constexpr int NCR = ROUNDS > 0 ? ROUNDS : 1;
@@ -1147,7 +1229,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(m0v) : "memory");
         }
 #endif
-        twiddle_store(xr, twa, twb, smem + p1f * kFS + n2 * 8);
+        twiddle_store<TWP2>(xr, twa, twb, smem + p1f * kFS + n2 * 8);
         SGX_STAMP(4);  // twiddles + ex writes
         unsigned next = lead + slots * HS + (BIN ? 0u : half);
         if (next >= hi) next -= BIN ? 0u : half;  // no tile of its own next round: repeat the first half's
@@ -1194,6 +1276,16 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
         }
         v2f A[16], B[16];
         read_rows((WIDE ? smem_all : smem) + p2ex * kFS, ra, rb, A, B);
+        if constexpr (TRLDS) {
+            const v4f *tq = (const v4f *)(tabs + kTrOff + j * 128u);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const v4f t2 = tq[q];
+                tr[2 * q] = (v2f){t2.x, t2.y};
+                tr[2 * q + 1] = (v2f){t2.z, t2.w};
+            }
+        }
+        if constexpr (TWP2) pass2_twiddle(A, B, tr);
         SGX_STAMP(7);  // row reads
         __syncthreads();  // barrier 4: ex consumed: the next staging (or the pw overlay) may overwrite it
         SGX_STAMP(8);
@@ -1214,7 +1306,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
         if constexpr (BIN) {
             const unsigned c1 = j == 0 ? 16u : j, c2 = j == 0 ? 0u : j + 256u;
             auto slot_of = [&](unsigned k) { return (float *)smem + (k * 16u + p2f) * 2u; };  // spec[k][f], bins k + 32 i at i * PSTEP
-            pass2_compute<MODE, AMP, false>(A, B, j == 0, eps, twj, make_rsrc(a.out, 0u), 0u, 0u, 0u, 0u, 0u, 0u, slot_of(c1),
+            pass2_compute<MODE, AMP, false, TWP2>(A, B, j == 0, eps, twj, make_rsrc(a.out, 0u), 0u, 0u, 0u, 0u, 0u, 0u, slot_of(c1),
                                             slot_of(512u - 224u - c1), slot_of(c2), slot_of(512u - 224u - c2), slot_of(256u) SGX_STAMP_ARGS);
             __syncthreads();  // both channels' spectra complete
             binaural_tile<AMP>(a, smem_all, b, f0, nf);
@@ -1247,7 +1339,7 @@ __global__ __launch_bounds__(512, 2) void k_r32x16(StftArgs a, unsigned per_xcd,
             const __amdgpu_buffer_rsrc_t ro = make_rsrc((unsigned char *)a.out + (size_t)p2b * 513u * a.n_frames * ES, (unsigned)obytes);
             {
                 auto slot_of = [&](unsigned k) { return pwf + (PWT ? pwt_index(k, p2f) : p2f * kPS + k); };  // bins k + 32 i follow at i * PSTEP
-                pass2_compute<MODE, AMP, PWT>(A, B, j == 0, eps, twj, ro, (jo.a1 + p2ofs) * ES, (jo.b1 + p2ofs) * ES, (jo.a2 + p2ofs) * ES,
+                pass2_compute<MODE, AMP, PWT, TWP2>(A, B, j == 0, eps, twj, ro, (jo.a1 + p2ofs) * ES, (jo.b1 + p2ofs) * ES, (jo.a2 + p2ofs) * ES,
                                                      (jo.b2 + p2ofs) * ES, (jo.mid + p2ofs) * ES, step, slot_of(c1), slot_of(512u - 224u - c1),
                                                      slot_of(c2), slot_of(512u - 224u - c2), slot_of(256u) SGX_STAMP_ARGS);
             }

@@ -13,8 +13,11 @@ constexpr int kExBytes = 16 * kFS;  // 65792: one tile's exchange buffer; also h
 constexpr int kOutOff = kExBytes - 16 * 17 * 128;  // 30976
 // tables behind the two exchange buffers
 constexpr int kWinOff = 0;                      // float2 win[512]: (w[2n], w[2n+1]) / 2
-constexpr int kTw2Off = 4096;                   // float4 tw2[16 jobs][17]: entry i of job j = (W', W'^perp) of the i-th pair it splits
-constexpr int kTw2Bytes = 16 * 17 * 16;         // row stride 272 B: jobs j and j + 4 (one read group) sit on different banks
+constexpr int kTw2Off = 4096;                   // float2 tw2[16 jobs][18]: entry i of job j = W' of the i-th pair it splits (host: (W', W'^perp))
+constexpr int kTw2Stride = 144;                 // bytes per job: 16-byte reads; jobs j, j + 4, j + 8, j + 12 (one read group) on different banks
+constexpr int kTw2Bytes = 16 * 17 * 16;         // 4352: the split twiddles (16 * kTw2Stride = 2304 B), then the pass-2 row twiddles:
+constexpr int kTrOff = kTw2Off + 16 * kTw2Stride;  // float2 tr[16 jobs][16] = W_512^(r n), r = the job's first row (kernels that read them from LDS)
+static_assert(kTrOff + 16 * 128 <= kTw2Off + kTw2Bytes, "row twiddles inside the table area");
 constexpr int kMelOff = kTw2Off + kTw2Bytes;    // filterbank schedule (below)
 constexpr int kMelMaxWords = 4096;
 constexpr int kLdsBytes = 2 * kExBytes + kMelOff + kMelMaxWords * 4;  // 156416 of the CU's 163840
