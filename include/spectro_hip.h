@@ -285,6 +285,11 @@ sgx_status sgx_fft2d_filter(sgx_fft2d *plan, const void *images, size_t batch, i
 sgx_status sgx_fft2d_reserve(sgx_fft2d *plan, size_t batch, int32_t host_staging);
 int32_t sgx_fft2d_device(const sgx_fft2d *plan); /* the HIP device ordinal the plan is bound to */
 const char *sgx_fft2d_last_error(const sgx_fft2d *plan);
+/* The route of the plan's last successful convolve / filter call (a failed call leaves it as it was): "separable" (rank-1 kernel,
+ * 1024 x 1024 f32: two passes over pairs of real rows), "colconv_outer" / "colconv_spectrum" / "colconv_mask" (f32, 1024 rows: the
+ * fused column kernel with a rank-1 kernel's two factors, a full kernel spectrum or a filter mask), each with "/chunked" when the
+ * batch ran as chunks on two streams, "unfused" (separate forward, product and inverse passes), or "" before any such call. */
+const char *sgx_fft2d_kernel_name(const sgx_fft2d *plan);
 
 /* ---- 1-D complex-to-complex plan: C2cPlan<T> (src/fft_backend.rs:113-137; `Sample::plan_c2c`, src/sample.rs:61-66).  In
  * place, UNNORMALISED in both directions (the caller divides by n after an inverse, as the trait says), host pointers, `len`

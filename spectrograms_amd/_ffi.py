@@ -27,7 +27,7 @@ SYMBOLS = [
     "sgx_r2c", "sgx_c2r", "sgx_istft", "sgx_istft_length", "sgx_window", "sgx_mel_weights", "sgx_shard_range", "sgx_last_error", "sgx_last_create_error",
     "sgx_kernel_name", "sgx_abi_version", "sgx_device_count",
     "sgx_fft2d_create", "sgx_fft2d_destroy", "sgx_fft2d_forward", "sgx_fft2d_inverse", "sgx_fft2d_convolve",
-    "sgx_fft2d_filter", "sgx_fft2d_last_error", "sgx_fft2d_reserve", "sgx_fft2d_device",
+    "sgx_fft2d_filter", "sgx_fft2d_last_error", "sgx_fft2d_reserve", "sgx_fft2d_device", "sgx_fft2d_kernel_name",
     "sgx_reserve", "sgx_plan_device", "sgx_last_dim_mismatch",
     "sgx_c2c_create", "sgx_c2c_destroy", "sgx_c2c_forward", "sgx_c2c_inverse", "sgx_c2c_last_error",
     "sgx_comm_unique_id", "sgx_comm_create", "sgx_comm_adopt", "sgx_comm_destroy", "sgx_comm_last_error", "sgx_gather", "sgx_shard_execute", "sgx_shard_execute_chunked",
@@ -145,6 +145,8 @@ def lib() -> C.CDLL:
     L.sgx_fft2d_reserve.argtypes = [vp, sz, C.c_int32]
     L.sgx_fft2d_device.argtypes = [vp]
     L.sgx_fft2d_device.restype = C.c_int32
+    L.sgx_fft2d_kernel_name.argtypes = [vp]
+    L.sgx_fft2d_kernel_name.restype = C.c_char_p
     L.sgx_reserve.argtypes = [vp, sz, sz, C.c_int32, C.c_int32]
     L.sgx_plan_device.argtypes = [vp]
     L.sgx_plan_device.restype = C.c_int32

@@ -50,6 +50,8 @@ struct sgx_fft2d {
     // second stream of the chunked convolve / filter schedule (fused_product_dev), forked from and joined to the caller's
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // route of the last successful convolve / filter call (sgx_fft2d_kernel_name): "" before any
+    const char *route = "";
     mutable std::string err;
 };
 
@@ -347,6 +349,15 @@ sgx_status fused_product_dev(sgx_fft2d *p, const void *img, size_t batch, const 
 
 bool use_fused(const sgx_fft2d *p) { return p->d_tw1c != nullptr; }
 
+// sgx_fft2d_kernel_name of a fused_product_dev call
+const char *fused_route(const sgx_fft2d *p, size_t batch, int mul_kind) {
+    const bool chunked = mul_kind != MUL_VEC && fused_chunked(p, batch);
+    return mul_kind == MUL_VEC     ? "separable"
+         : mul_kind == MUL_OUTER   ? (chunked ? "colconv_outer/chunked" : "colconv_outer")
+         : mul_kind == MUL_MASK    ? (chunked ? "colconv_mask/chunked" : "colconv_mask")
+                                   : (chunked ? "colconv_spectrum/chunked" : "colconv_spectrum");
+}
+
 // Is the kernel an outer product u v^T to f32 rounding?  Pivot on the largest |K|: u = its column, v = its row / the pivot, in f64; every
 // element within 2^-22 max|K| of u_i v_j (gaussian_kernel_2d, computed in f64 and rounded once to f32, is within 1.8e-7).  The kernel's
 // padded image (pad_kernel_for_fft, image_ops.rs:123-152: centre to (0,0), wrapped) is then the outer product of the two padded vectors
@@ -461,6 +472,8 @@ sgx_status sgx_fft2d_reserve(sgx_fft2d *p, size_t batch, int32_t host_staging) {
 }
 
 const char *sgx_fft2d_last_error(const sgx_fft2d *plan) { return plan ? plan->err.c_str() : g_err2d.c_str(); }
+
+const char *sgx_fft2d_kernel_name(const sgx_fft2d *plan) { return plan ? plan->route : ""; }
 
 sgx_status sgx_fft2d_create(size_t nrows, size_t ncols, int32_t dtype, int32_t device, sgx_fft2d **out) {
     if (out) *out = nullptr;
@@ -650,14 +663,16 @@ sgx_status sgx_fft2d_convolve(sgx_fft2d *p, const void *images, size_t batch, co
         p->kspec_valid = true;
     }
     const size_t imgb = batch * R * C * p->elem;
-    return with_staging(p, images, imgb, out, imgb, mem_kind, s, [&](const void *i, void *o) -> sgx_status {
-        if (use_fused(p) && p->kspec_outer) return fused_product_dev(p, i, batch, p->d_kouter, p->kspec_separable ? MUL_VEC : MUL_OUTER, o, s);
-        if (use_fused(p)) return fused_product_dev(p, i, batch, p->d_kspec, MUL_SPECTRUM, o, s);
+    const int kind = !use_fused(p) ? -1 : p->kspec_outer ? (p->kspec_separable ? MUL_VEC : MUL_OUTER) : MUL_SPECTRUM;
+    st = with_staging(p, images, imgb, out, imgb, mem_kind, s, [&](const void *i, void *o) -> sgx_status {
+        if (kind >= 0) return fused_product_dev(p, i, batch, p->kspec_outer ? p->d_kouter : p->d_kspec, kind, o, s);
         sgx_status s2 = grow2(p, &p->d_spec, &p->spec_bytes, batch * R * Cb * 2 * p->elem);
         if (s2 != SGX_OK) return s2;
         if ((s2 = forward_dev(p, i, batch, p->d_spec, s, p->d_kspec, 0)) != SGX_OK) return s2;
         return inverse_dev(p, p->d_spec, batch, o, s);
     });
+    if (st == SGX_OK) p->route = kind >= 0 ? fused_route(p, batch, kind) : "unfused";
+    return st;
 }
 
 sgx_status sgx_fft2d_filter(sgx_fft2d *p, const void *images, size_t batch, int32_t kind, double cut_lo, double cut_hi,
@@ -700,13 +715,15 @@ sgx_status sgx_fft2d_filter(sgx_fft2d *p, const void *images, size_t batch, int3
         p->mask_valid = true;
     }
     const size_t imgb = batch * R * C * p->elem;
-    return with_staging(p, images, imgb, out, imgb, mem_kind, s, [&](const void *i, void *o) -> sgx_status {
+    st = with_staging(p, images, imgb, out, imgb, mem_kind, s, [&](const void *i, void *o) -> sgx_status {
         if (use_fused(p)) return fused_product_dev(p, i, batch, p->d_mask, MUL_MASK, o, s);
         sgx_status s2 = grow2(p, &p->d_spec, &p->spec_bytes, batch * R * Cb * 2 * p->elem);
         if (s2 != SGX_OK) return s2;
         if ((s2 = forward_dev(p, i, batch, p->d_spec, s, p->d_mask, 1)) != SGX_OK) return s2;
         return inverse_dev(p, p->d_spec, batch, o, s);
     });
+    if (st == SGX_OK) p->route = use_fused(p) ? fused_route(p, batch, MUL_MASK) : "unfused";
+    return st;
 }
 
 }  // extern "C"

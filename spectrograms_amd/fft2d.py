@@ -32,6 +32,12 @@ class Fft2dPlan:
     def device(self) -> int:
         return self._device
 
+    @property
+    def kernel_name(self) -> str:
+        """The route of the last successful convolve / filter call ("separable", "colconv_outer", "colconv_spectrum", "colconv_mask", each with
+        "/chunked" when the two-stream schedule ran, "unfused"), "" before any."""
+        return self._lib.sgx_fft2d_kernel_name(self._h).decode()
+
     def reserve(self, batch: int, host_staging: bool = True) -> None:
         """Pre-size the plan-owned intermediates so that later calls of up to `batch` images do not allocate."""
         self._check(self._lib.sgx_fft2d_reserve(self._h, int(batch), int(host_staging)))
