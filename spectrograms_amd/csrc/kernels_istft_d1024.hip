@@ -460,11 +460,14 @@ __global__ __launch_bounds__(512, 2) void k_istft_d512(IstDArgs a, const v2d *tw
         {
             const double *w1 = (const double *)(smem + kI5Win) + n2;
             double *fa = (double *)smem + (2u * f2) * 512u + n2, *fb = fa + 512;
+            // a frame past the signal (the partner of an odd last frame) is zeros by a select: the imaginary part of its pair's transform
+            // holds the rounding of the last frame, which the overlap-add would put into the tail where the reference adds nothing
+            const bool vfb = F + 2u * f2 + 1u < a.n_frames;
 #pragma unroll
             for (int n1 = 0; n1 < 16; ++n1) {  // z[n] = conj(y[n]) / 512, n = n2 + 32 n1: frame 2 p = Re z, frame 2 p + 1 = Im z
                 const double ww = w1[32 * n1];
                 fa[32 * n1] = __dmul_rn(v[n1].x * a.scale, ww);
-                fb[32 * n1] = __dmul_rn(-v[n1].y * a.scale, ww);
+                fb[32 * n1] = vfb ? __dmul_rn(-v[n1].y * a.scale, ww) : 0.0;
             }
         }
         __syncthreads();

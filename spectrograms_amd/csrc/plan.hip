@@ -1362,9 +1362,11 @@ sgx_status inverse_tables(sgx_plan *pl) {
     return SGX_OK;
 }
 
-// frames (rows) of `spec` -> real rows of n_fft samples: inverse real FFT, * 1/n in T (fft_backend.rs:559-563), optional window
+// frames (rows) of `spec` -> real rows of n_fft samples: inverse real FFT, * 1/n in T (fft_backend.rs:559-563), optional window.
+// `*route` is set to the rows' launcher that ran: "c2r_reg", "c2r_chirpz" (two rows per complex sequence), "c2r_chirpz_half",
+// "c2r_rows" (radix-2 / two-factor / direct sum), "big" (two rows per sequence)
 sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_t batch, size_t n_frames, bool frame_fast,
-                             const void *win, hipStream_t s) {
+                             const void *win, hipStream_t s, const char **route) {
     const unsigned n = pl->p.n_fft;
     C2rArgs c{};
     c.in = spec; c.out = frames;
@@ -1381,6 +1383,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
         sgx_status st = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, batch * ((n_frames + 1) / 2)));
         if (st != SGX_OK) return st;
         SGX_HIP(pl, launch_big_c2r(pl->big, c, pl->d_big, pl->dtype, s));
+        *route = "big";
         return SGX_OK;
     }
     c.tile = c2r_tile_for(n, pl->dtype, 144 * 1024);
@@ -1392,21 +1395,34 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
     c.bad_flag = (unsigned *)pl->d_flag;
     // register-tiled passes; at lengths without a split the chirp-z rows (a plan of such a length carries the tables); else the
     // LDS-tile rows (radix-2 / two-factor / direct sum)
+    const char *r = "c2r_reg";
     hipError_t e = launch_c2r_reg(c, pl->dtype, s);
 #ifndef SGX_NO_BS_C2C
     if (e == hipErrorNotSupported && pl->d_bs_bhp && (n & (n - 1)) != 0) {
         BsDevTables t;
         t.M = pl->bs_M; t.chirp = pl->d_bs_chirp; t.bhp = pl->d_bs_bhp; t.tw = pl->d_bs_tw;
+        r = "c2r_chirpz";
         e = launch_c2r_bluestein(c, t, pl->dtype, s);
     }
 #endif
-    if (e == hipErrorNotSupported && pl->bs_half.M) e = launch_c2r_bluestein(c, pl->bs_half, pl->dtype, s, true);
-    if (e == hipErrorNotSupported) e = launch_c2r_rows(c, pl->dtype, s);
+    if (e == hipErrorNotSupported && pl->bs_half.M) {
+        r = "c2r_chirpz_half";
+        e = launch_c2r_bluestein(c, pl->bs_half, pl->dtype, s, true);
+    }
+    if (e == hipErrorNotSupported) {
+        r = "c2r_rows";
+        e = launch_c2r_rows(c, pl->dtype, s);
+    }
     SGX_HIP(pl, e);
+    *route = r;
     return SGX_OK;
 }
 
-sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_frames, void *out, size_t out_len, hipStream_t s) {
+// `*route` is set to the route that ran (sgx_istft_kernel_name).  Every name it can take — keep tests/test_istft_precision.py's
+// list in step: "istft1024c", "istft2048", "istft_d512", "istft_d1024", "istft_reg", and launch_c2r_frames' rows + k_istft_ola:
+// "c2r_reg+ola", "c2r_chirpz+ola", "c2r_chirpz_half+ola", "c2r_rows+ola", "big+ola" (sgx_c2r: the same rows without "+ola")
+sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_frames, void *out, size_t out_len, hipStream_t s,
+                     const char **route) {
     sgx_status st;
     const size_t n = pl->p.n_fft;
     SGX_HIP(pl, hipMemsetAsync(pl->d_flag, 0, sizeof(unsigned), s));
@@ -1417,6 +1433,7 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
         SGX_HIP(pl, launch_istft1024(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch),
                                      out_len == full0 ? 0 : pad0, out_len, 1.0f / 1024.0f, (unsigned *)pl->d_flag, pl->d_itwr,
                                      pl->d_itw1, s));
+        *route = "istft1024c";
         return SGX_OK;
     }
     const size_t pad = pl->p.centre ? n / 2 : 0;
@@ -1425,16 +1442,19 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
     if (pl->d_itwr2 && n_frames * 1025ull * 8ull < 0x7fffffffull) {  // fused tuned kernel at n_fft 2048 (kernels_istft2048.hip)
         SGX_HIP(pl, launch_istft2048(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0f / 2048.0f,
                                      (unsigned *)pl->d_flag, pl->d_itwr2, pl->d_itw12, s));
+        *route = "istft2048";
         return SGX_OK;
     }
     if (pl->istft_d512 && n_frames * 257ull * 16ull < 0x7fffffffull) {  // fused f64 kernel at n_fft 512 (kernels_istft_d1024.hip: k_istft_d512)
         SGX_HIP(pl, launch_istft_d512(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0 / 512.0,
                                       (unsigned *)pl->d_flag, pl->d_itw1d, s));
+        *route = "istft_d512";
         return SGX_OK;
     }
     if (pl->d_itwrd && n_frames * 513ull * 16ull < 0x7fffffffull) {  // fused tuned f64 kernel at n_fft 1024 (kernels_istft_d1024.hip)
         SGX_HIP(pl, launch_istft_d1024(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0 / 1024.0,
                                        (unsigned *)pl->d_flag, pl->d_itwrd, pl->d_itw1d, s));
+        *route = "istft_d1024";
         return SGX_OK;
     }
     // fused register-tiled kernel (every length with a pass split, hop <= n_fft, at most half a tile of halo frames): the windowed
@@ -1443,13 +1463,21 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
         const hipError_t e = launch_istft_reg(spec, out, pl->d_window, pl->d_itw, unsigned(n), unsigned(n_frames), pl->p.hop_size, unsigned(batch),
                                               start, out_len, pl->dtype == SGX_F64 ? 1.0 / double(n) : double(1.0f / float(n)),
                                               (unsigned *)pl->d_flag, pl->dtype, s);
-        if (e == hipSuccess) return SGX_OK;
+        if (e == hipSuccess) {
+            *route = "istft_reg";
+            return SGX_OK;
+        }
         if (e != hipErrorNotSupported) SGX_HIP(pl, e);
     }
     if ((st = grow(pl, &pl->d_frames, &pl->d_frames_bytes, batch * n_frames * n * pl->elem)) != SGX_OK) return st;
-    if ((st = launch_c2r_frames(pl, spec, pl->d_frames, batch, n_frames, true, pl->d_window, s)) != SGX_OK) return st;
+    const char *rows = "";
+    if ((st = launch_c2r_frames(pl, spec, pl->d_frames, batch, n_frames, true, pl->d_window, s, &rows)) != SGX_OK) return st;
     SGX_HIP(pl, launch_istft_ola(pl->d_frames, pl->d_window, out, unsigned(n), pl->p.hop_size, unsigned(n_frames), start, out_len,
                                  unsigned(batch), pl->dtype, s));
+    static const char *const with_ola[][2] = {{"c2r_reg", "c2r_reg+ola"}, {"c2r_chirpz", "c2r_chirpz+ola"},
+                                              {"c2r_chirpz_half", "c2r_chirpz_half+ola"}, {"c2r_rows", "c2r_rows+ola"}, {"big", "big+ola"}};
+    for (const auto &p : with_ola)
+        if (std::strcmp(p[0], rows) == 0) *route = p[1];
     return SGX_OK;
 }
 
@@ -1476,6 +1504,8 @@ int32_t sgx_device_count(void) {
 
 const char *sgx_last_create_error(void) { return g_create_err.c_str(); }
 const char *sgx_last_error(const sgx_plan *plan) { return plan ? plan->err.c_str() : g_create_err.c_str(); }
+
+const char *sgx_istft_kernel_name(const sgx_plan *plan) { return plan ? plan->istft_route : ""; }
 
 const char *sgx_kernel_name(const sgx_plan *plan) {
     if (!plan) return "";
@@ -1903,16 +1933,21 @@ sgx_status sgx_istft(sgx_plan *plan, const void *stft, size_t batch, size_t n_bi
     DeviceGuard dg;
     SGX_HIP(plan, dg.enter(plan->device));
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (mem_kind == SGX_MEM_DEVICE) return run_istft(plan, stft, batch, n_frames, out, len, s);
+    const char *route = "";
+    sgx_status st;
+    if (mem_kind == SGX_MEM_DEVICE) {
+        if ((st = run_istft(plan, stft, batch, n_frames, out, len, s, &route)) == SGX_OK) plan->istft_route = route;
+        return st;
+    }
     if (mem_kind != SGX_MEM_HOST) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     const size_t in_bytes = batch * n_bins * n_frames * 2 * plan->elem, out_bytes = out_elems * plan->elem;
-    sgx_status st;
     if ((st = grow(plan, &plan->d_in, &plan->d_in_bytes, in_bytes)) != SGX_OK) return st;
     if ((st = grow(plan, &plan->d_out, &plan->d_out_bytes, out_bytes)) != SGX_OK) return st;
     SGX_HIP(plan, hipMemcpyAsync(plan->d_in, stft, in_bytes, hipMemcpyHostToDevice, s));
-    if ((st = run_istft(plan, plan->d_in, batch, n_frames, plan->d_out, len, s)) != SGX_OK) return st;
+    if ((st = run_istft(plan, plan->d_in, batch, n_frames, plan->d_out, len, s, &route)) != SGX_OK) return st;
     SGX_HIP(plan, hipMemcpyAsync(out, plan->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    return check_flag(plan, s);  // synchronises
+    if ((st = check_flag(plan, s)) == SGX_OK) plan->istft_route = route;  // (synchronises)
+    return st;
 }
 
 sgx_status sgx_c2r(sgx_plan *plan, const void *in, size_t in_len, void *out, size_t out_len) {
@@ -1931,9 +1966,11 @@ sgx_status sgx_c2r(sgx_plan *plan, const void *in, size_t in_len, void *out, siz
     sgx_status st;
     SGX_HIP(plan, hipMemcpy(plan->d_in, in, 2 * nb * plan->elem, hipMemcpyHostToDevice));
     SGX_HIP(plan, hipMemsetAsync(plan->d_flag, 0, sizeof(unsigned), nullptr));
-    if ((st = launch_c2r_frames(plan, plan->d_in, plan->d_out, 1, 1, false, nullptr, nullptr)) != SGX_OK) return st;
+    const char *route = "";
+    if ((st = launch_c2r_frames(plan, plan->d_in, plan->d_out, 1, 1, false, nullptr, nullptr, &route)) != SGX_OK) return st;
     SGX_HIP(plan, hipMemcpy(out, plan->d_out, n * plan->elem, hipMemcpyDeviceToHost));
-    return check_flag(plan, nullptr);
+    if ((st = check_flag(plan, nullptr)) == SGX_OK) plan->istft_route = route;
+    return st;
 }
 
 int32_t sgx_plan_device(const sgx_plan *plan) { return plan ? plan->device : -2; }

@@ -432,6 +432,7 @@ struct sgx_plan {
     bool bs_fwd_half = false;  // K_BLUESTEIN in half-length complex form (even n_fft whose own convolution does not fit LDS)
     sgx::BsDevTables bs_half;  // inverse rows of an even n_fft whose own chirp-z does not fit: tables of length n_fft / 2 (inverse_tables)
     size_t d_frames_bytes = 0;
+    const char *istft_route = "";  // route of the last successful sgx_istft / sgx_c2r (sgx_istft_kernel_name): "" before any
     // K_BIGFFT: tables of the global-memory transforms and their sequence scratch (grown on demand, pre-sized by sgx_reserve)
     sgx::BigDev big;
     unsigned big_n = 0;  // set at creation when the plan's kind is K_BIGFFT (host-only plans have no tables)

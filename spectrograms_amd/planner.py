@@ -267,6 +267,11 @@ class Plan:
     def kernel_name(self) -> str:
         return self._lib.sgx_kernel_name(self._h).decode()
 
+    @property
+    def istft_kernel_name(self) -> str:
+        """Route of the last successful istft_batch / istft / c2r call (sgx_istft_kernel_name); "" before any."""
+        return self._lib.sgx_istft_kernel_name(self._h).decode()
+
     def output_shape(self, signal_length: int) -> Tuple[int, int]:
         if int(signal_length) <= 0:
             raise ValueError("signal_length must be > 0")

@@ -15,8 +15,8 @@ run packed tiles on into the next signal, and the fused MFCC epilogue reads padd
      band m     |dM_m| <= sum_k w_mk dP_k + L_m u_T sum_k w_mk P_k      (L_m = nonzero weights of band m)
    On the pairing routes ||x_f w|| is the pair's joint norm sqrt(||x_a w||^2 + ||x_b w||^2).  The CPU calibration shows the strict bound
    is neither loose nor vacuous: a per-frame f32 FFT meets it, a paired one (z = a + i b) breaks it and meets the joint one.
-4. The inverse routes: a NaN / Inf bin in a middle and in the last frame of signal 1 reaches the samples of that frame (and its
-   partner's, on the pairing routes) and nothing else.
+4. The inverse routes (one case per `Plan.istft_kernel_name`, asserted): a NaN / Inf bin in a middle and in the last frame of signal 1
+   reaches the samples of that frame (and its partner's, on the pairing routes) and nothing else.
 """
 import math
 
@@ -509,17 +509,24 @@ def test_bound_calibration_per_frame_meets_paired_breaks():
 
 
 # ---- 4. inverse routes ---------------------------------------------------------------------------------------------------------
-# (dtype, n_fft, hop, inverse, frames pair up); the inverse follows the forward table of DESIGN.md §3
-INVERSE = [("float32", 1024, 256, "k_istft1024c", False), ("float32", 2048, 512, "k_istft2048", False),
-           ("float64", 1024, 256, "k_istft_d1024", False), ("float64", 512, 160, "k_istft_d512", True),
-           ("float32", 512, 128, "k_c2r_reg", False), ("float32", 400, 160, "k_c2r_reg", False),
-           ("float64", 32768, 8192, "bigfft", True)]
+# (dtype, n_fft, hop, inverse, frames pair up, Plan.istft_kernel_name); one case per inverse route name, pairing read from the code:
+# k_istft_d512 (two frames per transform), the chirp-z rows (launch_c2r_bluestein's full form: nseq = row pairs) and bigfft
+INVERSE = [("float32", 1024, 256, "k_istft1024c", False, "istft1024c"), ("float32", 2048, 512, "k_istft2048", False, "istft2048"),
+           ("float64", 1024, 256, "k_istft_d1024", False, "istft_d1024"), ("float64", 512, 160, "k_istft_d512", True, "istft_d512"),
+           ("float32", 512, 128, "k_c2r_reg", False, "istft_reg"), ("float32", 400, 160, "k_c2r_reg", False, "istft_reg"),
+           ("float64", 32768, 8192, "bigfft", True, "big+ola"),
+           ("float32", 251, 62, "k_bs_c2c", True, "c2r_chirpz+ola"), ("float64", 1009, 252, "k_bs_c2c", True, "c2r_chirpz+ola"),
+           ("float64", 6000, 1500, "k_bs_c2c_half", False, "c2r_chirpz_half+ola"),
+           ("float32", 8200, 2050, "k_bs_c2c_half", False, "c2r_chirpz_half+ola"),
+           ("float32", 15, 4, "k_c2r_rows", False, "c2r_rows+ola"), ("float64", 13, 4, "k_c2r_rows", False, "c2r_rows+ola"),
+           ("float64", 400, 160, "k_c2r_reg+ola", False, "c2r_reg+ola"), ("float32", 1024, 63, "k_c2r_reg+ola", False, "c2r_reg+ola"),
+           ("float32", 9001, 2250, "bigfft", True, "big+ola")]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", INVERSE, ids=lambda c: f"{c[3]}-{c[0][5:]}-{c[1]}-{c[2]}")
 def test_gpu_inverse_non_finite_bin_stays_in_its_frame(case):
-    dtype, n_fft, hop, _, pairs = case
+    dtype, n_fft, hop, _, pairs, route = case
     nf = min(41, max(5, 40000 // hop) | 1)
     n = n_samples(hop, n_fft, nf)
     plan = make_plan(dtype, n_fft, hop, "complex")
@@ -529,6 +536,7 @@ def test_gpu_inverse_non_finite_bin_stays_in_its_frame(case):
     S[1, 5, fm] = 0
     S[1, 5, nf - 1] = 0
     base = plan.istft_batch(S)
+    assert plan.istft_kernel_name == route
     L = base.shape[1]
     for f in (fm, nf - 1):
         own = np.zeros(L, bool)
