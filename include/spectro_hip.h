@@ -325,6 +325,13 @@ const char *sgx_kernel_name(const sgx_plan *plan);
  * "istft2048", "istft_d512", "istft_d1024", "istft_reg", or rows into a frame scratch then the overlap-add, "c2r_reg+ola",
  * "c2r_chirpz+ola", "c2r_chirpz_half+ola", "c2r_rows+ola", "big+ola"; sgx_c2r: the same rows without "+ola". */
 const char *sgx_istft_kernel_name(const sgx_plan *plan);
+/* Filterbank stage (Mel / log-Hz / ERB / chroma rows, MFCC on top) of the plan's last successful sgx_execute / sgx_execute_timed call,
+ * "" before any and for plans without a bank (a diagnostic, like sgx_kernel_name: the bank's shape decides which device code applies it).
+ * In the launch sgx_kernel_name names: "r32x16_sched", "r32x16_sched_packed" (batches of short signals), "r32x16_sched512", "r32x16_sched_mfcc" (MFCC in the same launch), "r32x16_mfma",
+ * "r32x16_csr", "r32x32_sched", "r64x32_sched", "d32x16_sched", "d512_sched", "d32x32_sched", "reg_radix_bands", "reg_radix_csr",
+ * "generic_csr", "bluestein_rows"; "bank_rows": per-bin values from that launch, the rows in a second one.  A separate MFCC launch behind
+ * the stage appends "+mfcc_acc" or "+mfcc_rows". */
+const char *sgx_bank_stage_name(const sgx_plan *plan);
 int32_t sgx_abi_version(void);
 int32_t sgx_device_count(void);
 

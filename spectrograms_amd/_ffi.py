@@ -25,7 +25,7 @@ DEVICE_CURRENT, DEVICE_HOST_ONLY = -1, -2
 SYMBOLS = [
     "sgx_plan_create", "sgx_plan_destroy", "sgx_output_shape", "sgx_execute", "sgx_execute_timed", "sgx_axes",
     "sgx_r2c", "sgx_c2r", "sgx_istft", "sgx_istft_length", "sgx_window", "sgx_mel_weights", "sgx_shard_range", "sgx_last_error", "sgx_last_create_error",
-    "sgx_kernel_name", "sgx_istft_kernel_name", "sgx_abi_version", "sgx_device_count",
+    "sgx_kernel_name", "sgx_istft_kernel_name", "sgx_bank_stage_name", "sgx_abi_version", "sgx_device_count",
     "sgx_fft2d_create", "sgx_fft2d_destroy", "sgx_fft2d_forward", "sgx_fft2d_inverse", "sgx_fft2d_convolve",
     "sgx_fft2d_filter", "sgx_fft2d_last_error", "sgx_fft2d_reserve", "sgx_fft2d_device", "sgx_fft2d_kernel_name",
     "sgx_reserve", "sgx_plan_device", "sgx_last_dim_mismatch",
@@ -133,6 +133,8 @@ def lib() -> C.CDLL:
     L.sgx_kernel_name.restype = C.c_char_p
     L.sgx_istft_kernel_name.argtypes = [vp]
     L.sgx_istft_kernel_name.restype = C.c_char_p
+    L.sgx_bank_stage_name.argtypes = [vp]
+    L.sgx_bank_stage_name.restype = C.c_char_p
     L.sgx_abi_version.restype = C.c_int32
     L.sgx_device_count.restype = C.c_int32
     L.sgx_fft2d_create.argtypes = [sz, sz, C.c_int32, C.c_int32, C.POINTER(vp)]

@@ -700,6 +700,7 @@ hipError_t run_fused(const BsArgs &a, int dtype, hipStream_t s) {
     f.wc = a.wc; f.chirp = a.chirp; f.bhp = a.bhat_fused; f.tw = a.tw_m;
     f.complex_out = a.complex_out; f.amp = a.amp; f.eps = a.eps;
     f.mel_ptr = a.mel_ptr; f.mel_col = a.mel_col; f.mel_val = a.mel_val; f.n_mels = a.n_mels; f.n_out = a.n_out;
+    if (f.mel_ptr) note_bank_stage("bluestein_rows");
 #define SGX_BSF_F32(A, B, C) if (fa == A && fb == B && fc == C) return launch_fused_t<float, A, B, C>(f, ltile, lds, s);
 #define SGX_BSF_F64(A, B, C) if (fa == A && fb == B && fc == C) return launch_fused_t<double, A, B, C>(f, ltile, lds, s);
     if (dtype == SGX_F64) {

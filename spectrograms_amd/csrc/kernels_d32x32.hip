@@ -294,6 +294,7 @@ __global__ __launch_bounds__(512, 2) void k_d32x32(StftArgs a, unsigned per_xcd,
 
 template <int MODE, int AMP>
 hipError_t launch_variant_e(const StftArgs &a, hipStream_t s) {
+    if (MODE == OUT_MEL) note_bank_stage("d32x32_sched");  // (the only bank stage of this kernel: plan_geometry refuses a bank without a schedule)
     const unsigned total = a.tiles * a.batch;
     const unsigned per_xcd = (total + 7u) / 8u;
     const unsigned cu_slots = std::max(1u, device_cu_count() / 8u);

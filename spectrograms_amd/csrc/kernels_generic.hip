@@ -1149,6 +1149,7 @@ hipError_t launch_reg_radix(const StftArgs &a, int dtype, hipStream_t s) {
         csr_lds = (unsigned)csr;
         lds += csr;
     }
+    if (a.out_mode == OUT_MEL) note_bank_stage(band_lds ? "reg_radix_bands" : "reg_radix_csr");
 #define SGX_RR_F32(A, B, C) \
     if (fa == A && fb == B && fc == C) return launch_reg_radix_t<float, A, B, C>(a, (unsigned)g, lds, csr_lds, band_lds, staged, s);
 #define SGX_RR_F64(A, B, C) \
@@ -1168,6 +1169,7 @@ hipError_t launch_reg_radix(const StftArgs &a, int dtype, hipStream_t s) {
 hipError_t launch_lds_radix2(const StftArgs &a, int dtype, hipStream_t s) {
     unsigned long long g;
     if (!grid_ok(a, &g)) return hipErrorInvalidConfiguration;
+    if (a.out_mode == OUT_MEL) note_bank_stage("generic_csr");  // mel_stage
     size_t es = elem_size(dtype);
     size_t lds = (size_t)a.ft * (a.m + 1) * 2 * es + (a.out_mode == OUT_MEL ? (size_t)a.ft * a.nb_fft * es : 0);
     if (a.tw_lds) lds = (size_t)a.tw_lds + (size_t)a.m * 2 * es;
@@ -1182,6 +1184,7 @@ hipError_t launch_lds_radix2(const StftArgs &a, int dtype, hipStream_t s) {
 hipError_t launch_direct_dft(const StftArgs &a, int dtype, hipStream_t s) {
     unsigned long long g;
     if (!grid_ok(a, &g)) return hipErrorInvalidConfiguration;
+    if (a.out_mode == OUT_MEL) note_bank_stage("generic_csr");  // mel_stage
     size_t es = elem_size(dtype);
     size_t lds = (size_t)a.ft * a.n_fft * es + (a.out_mode == OUT_MEL ? (size_t)a.ft * a.nb_fft * es : 0);
     if (hipError_t e = dtype == SGX_F64 ? lds_opt_in(k_direct_dft<double>, lds) : lds_opt_in(k_direct_dft<float>, lds); e != hipSuccess) return e;
@@ -1195,6 +1198,7 @@ hipError_t launch_direct_dft(const StftArgs &a, int dtype, hipStream_t s) {
 hipError_t launch_two_factor(const StftArgs &a, int dtype, hipStream_t s) {
     unsigned long long g;
     if (!grid_ok(a, &g) || a.fac_a < 2 || a.fac_a * a.fac_b != a.n_fft) return hipErrorInvalidConfiguration;
+    if (a.out_mode == OUT_MEL) note_bank_stage("generic_csr");  // mel_stage
     const size_t lds = two_factor_bytes(a, a.ft, elem_size(dtype)) - (a.tw_lds ? 0 : (size_t)a.n_fft * 2 * elem_size(dtype));
     if (hipError_t e = dtype == SGX_F64 ? lds_opt_in(k_two_factor<double>, lds) : lds_opt_in(k_two_factor<float>, lds); e != hipSuccess) return e;
     if (dtype == SGX_F64)
@@ -1226,6 +1230,7 @@ hipError_t launch_bank_rows(const void *pw, void *out, const StftArgs &a, int dt
     const unsigned long long gx = (unsigned long long)fblocks * a.batch;
     if (gx == 0 || gx >= 0x7fffffffull || a.n_mels == 0 || a.n_mels > 65535u) return hipErrorInvalidConfiguration;
     const dim3 grid((unsigned)gx, a.n_mels);
+    note_bank_stage("bank_rows");
     if (dtype == SGX_F64)
         hipLaunchKernelGGL(k_bank_rows<double>, grid, dim3(64), 0, s, (const double *)pw, (double *)out, a.mel_ptr, a.mel_col,
                            (const double *)a.mel_val, a.nb_fft, a.n_mels, a.n_frames, fblocks, a.amp, (double)a.eps);
@@ -1246,6 +1251,7 @@ hipError_t launch_mfcc(const void *mel, void *out, const void *basis, const void
                        (T *)out, (const T *)basis, (const T *)lifter, batch, n_mels, n_frames, n_mfcc, skip, has_lifter)
     const int nc = n_mfcc <= 16 ? 16 : n_mfcc <= 32 ? 32 : n_mfcc <= 64 ? 64 : 0;
     if (nc && (size_t)n_mels * nc * es <= 48 * 1024) {
+        note_bank_stage("+mfcc_acc");
         if (dtype == SGX_F64) {
             if (nc == 16) SGX_MFCC_ACC(double, 16); else if (nc == 32) SGX_MFCC_ACC(double, 32); else SGX_MFCC_ACC(double, 64);
         } else {
@@ -1254,6 +1260,7 @@ hipError_t launch_mfcc(const void *mel, void *out, const void *basis, const void
         return hipGetLastError();
     }
 #undef SGX_MFCC_ACC
+    note_bank_stage("+mfcc_rows");
     if (dtype == SGX_F64)
         hipLaunchKernelGGL(k_mfcc<double>, dim3((unsigned)blocks), dim3(256), 0, s, (const double *)mel, (double *)out,
                            (const double *)basis, (const double *)lifter, batch, n_mels, n_frames, n_mfcc, skip, has_lifter);

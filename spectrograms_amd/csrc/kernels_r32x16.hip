@@ -1433,10 +1433,14 @@ hipError_t launch_variant(const StftArgs &a0, hipStream_t s) {
     constexpr bool W = MODE != OUT_MEL;
     if constexpr (MODE != OUT_MEL)
         if (pack && a.n_fft == 512u) return go(k_r32x16<MODE, AMP, 0, false, false, false, 128, true>);  // (128: any hop, the mode's marker)
-    if (pack) return go(k_r32x16<MODE, AMP, 0, false, false, MODE == OUT_MEL, 0, true>);
+    if (pack) {
+        if (MODE == OUT_MEL) note_bank_stage("r32x16_sched_packed");  // (want_pack: scheduled banks at n_fft 1024 only)
+        return go(k_r32x16<MODE, AMP, 0, false, false, MODE == OUT_MEL, 0, true>);
+    }
     if constexpr (MODE == OUT_MEL) {
         if (pwt) {
             if (a.n_fft == 512u) {  // two frames per transform
+                note_bank_stage("r32x16_sched512");
                 if (a.hop == 64u) return go(k_r32x16<MODE, AMP, 3, false, false, true, 64>);
                 if (a.hop == 128u) return go(k_r32x16<MODE, AMP, 5, false, false, true, 128>);
                 if (a.hop == 160u) return go(k_r32x16<MODE, AMP, 6, false, false, true, 160>);
@@ -1448,6 +1452,7 @@ hipError_t launch_variant(const StftArgs &a0, hipStream_t s) {
                 if (a.mfcc_frag && a.n_fft == 1024u) {  // Mel-dB -> DCT-II + lifter in the same launch (mfcc_tile)
                     const unsigned lds = (unsigned)kLdsBytes - (unsigned)kMelMaxWords * 4u + ((a.mel_sched_words + 3u) & ~3u) * 4u + a.mfcc_frag_words * 4u + 64u;
                     if (lds > 163840u) return hipErrorInvalidConfiguration;
+                    note_bank_stage("r32x16_sched_mfcc");
                     const unsigned ldsz = lds < (unsigned)kLdsBytes ? (unsigned)kLdsBytes : lds;
                     auto mf = [&](auto steps) -> hipError_t {
                         constexpr int S = decltype(steps)::value;
@@ -1462,6 +1467,7 @@ hipError_t launch_variant(const StftArgs &a0, hipStream_t s) {
                     return hipErrorInvalidConfiguration;
                 }
             }
+            note_bank_stage("r32x16_sched");
             if (a.hop == 256u) return go(k_r32x16<MODE, AMP, 5, false, true, true>);
             if (chunks <= 5u * 256u) return go(k_r32x16<MODE, AMP, 5, false, false, true>);
             return go(k_r32x16<MODE, AMP, 0, false, false, true>);
@@ -1477,6 +1483,7 @@ hipError_t launch_variant(const StftArgs &a0, hipStream_t s) {
         }
     }
     if (a.n_fft != 1024u) return hipErrorInvalidConfiguration;
+    if (MODE == OUT_MEL) note_bank_stage(a.mm_frag ? "r32x16_mfma" : "r32x16_csr");  // (the kernel's own branch after the |X|^2 tile)
     if (a.hop == 256u) return go(k_r32x16<MODE, AMP, 5, W, true, false>);
     if (chunks <= 5u * 256u) return go(k_r32x16<MODE, AMP, 5, W, false, false>);
     return go(k_r32x16<MODE, AMP, 0, W, false, false>);

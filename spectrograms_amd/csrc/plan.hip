@@ -40,6 +40,7 @@ constexpr unsigned kBigMin = 2048;  // frame lengths above this never run an O(n
 namespace {
 
 thread_local std::string g_create_err;
+thread_local const char *t_bank_stage = "", *t_bank_epilogue = "";  // filterbank stage of the call in flight: sgx::note_bank_stage below, read by run_device
 
 constexpr double kPi = 3.14159265358979323846264338327950288;
 
@@ -1165,6 +1166,7 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
     StftArgs a;
     void *stage_out = out;
     bool mfcc = pl->p.n_mfcc > 0;
+    t_bank_stage = t_bank_epilogue = "";
     KernelKind kind = pick_kernel(pl, x, stride);
     // MFCC: fused into the tuned kernel's launch where the plan carries the basis fragments AND this call stays on that kernel (a call may
     // step down the chain, e.g. signals of fewer frames than half a tile); else the Mel-dB tensor goes to plan-owned scratch
@@ -1222,6 +1224,8 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
         SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
         *ms = t / float(iters);
     }
+    pl->bank_stage = t_bank_stage;  // (string literals: the name is put together when it is asked for)
+    pl->bank_epilogue = t_bank_epilogue;
     return SGX_OK;
 }
 
@@ -1506,6 +1510,12 @@ const char *sgx_last_create_error(void) { return g_create_err.c_str(); }
 const char *sgx_last_error(const sgx_plan *plan) { return plan ? plan->err.c_str() : g_create_err.c_str(); }
 
 const char *sgx_istft_kernel_name(const sgx_plan *plan) { return plan ? plan->istft_route : ""; }
+
+const char *sgx_bank_stage_name(const sgx_plan *plan) {
+    if (!plan) return "";
+    plan->bank_stage_text.assign(plan->bank_stage).append(plan->bank_epilogue);
+    return plan->bank_stage_text.c_str();
+}
 
 const char *sgx_kernel_name(const sgx_plan *plan) {
     if (!plan) return "";
@@ -2046,5 +2056,18 @@ sgx_status sgx_shard_range(size_t batch, int32_t world_size, int32_t rank, size_
 }  // extern "C"
 
 namespace sgx {
+// Filterbank stage of the call in flight (sgx_bank_stage_name).  Every launcher that picks a piece of bank code says which one here;
+// run_device clears it before its launches and copies it into the plan once all of them went out.  A name starting with '+' is an
+// epilogue behind the bank stage and is appended to it (sgx_bank_stage_name).  Every name — keep tests/test_bank_readback.py's NAMES in step:
+//   "r32x16_sched" (mel_tile_sched, n_fft 1024, one-signal tiles), "r32x16_sched_packed" (its PACK form: tiles that run on into the
+//   next signals, batches of short signals), "r32x16_sched512" (mel_tile_sched512),
+//   "r32x16_sched_mfcc" (mel_tile_sched into the LDS tile + mfcc_tile, one launch), "r32x16_mfma" (map_tile_mfma), "r32x16_csr" (mel_tile_csr),
+//   "r32x32_sched", "r64x32_sched", "d32x16_sched", "d512_sched", "d32x32_sched" (the scheduled stage of each of those kernels),
+//   "reg_radix_bands" (k_reg_radix, padded band table in LDS), "reg_radix_csr" (k_reg_radix, CSR rows from LDS or global memory),
+//   "generic_csr" (mel_stage of k_lds_radix2 / k_two_factor / k_direct_dft), "bluestein_rows" (the chirp-z kernel's in-kernel rows),
+//   "bank_rows" (k_bank_rows: the second launch of the split path),
+//   and behind any of them but "r32x16_sched_mfcc": "+mfcc_acc" (k_mfcc_acc), "+mfcc_rows" (k_mfcc).
+void note_bank_stage(const char *name) { (name[0] == '+' ? t_bank_epilogue : t_bank_stage) = name; }
+
 void make_window_f64(const sgx_params &p, const std::vector<double> &custom, std::vector<double> &w) { build_window(p, custom, w); }
 }  // namespace sgx

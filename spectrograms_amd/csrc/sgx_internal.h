@@ -124,6 +124,9 @@ hipError_t launch_reg_radix(const StftArgs &a, int dtype, hipStream_t s);
 // filterbank rows over a [batch][nb_fft][n_frames] power / magnitude tensor (split filterbank path): CSR bank, amp and eps from `a`
 hipError_t launch_bank_rows(const void *pw, void *out, const StftArgs &a, int dtype, hipStream_t s);
 bool plan_geometry_r32x16_f32(StftArgs &a);
+// Filterbank stage of the launch being chosen (sgx_bank_stage_name; the names: plan.hip, beside its definition).  Called by the
+// launcher at the point where it picks the device code; run_device keeps it once the call has succeeded.
+void note_bank_stage(const char *name);
 
 // chirp-z (Bluestein) forward frames on the power-of-two complex kernels (bluestein.hip): lengths with a large prime factor
 struct BsArgs {
@@ -432,6 +435,8 @@ struct sgx_plan {
     bool bs_fwd_half = false;  // K_BLUESTEIN in half-length complex form (even n_fft whose own convolution does not fit LDS)
     sgx::BsDevTables bs_half;  // inverse rows of an even n_fft whose own chirp-z does not fit: tables of length n_fft / 2 (inverse_tables)
     size_t d_frames_bytes = 0;
+    const char *bank_stage = "", *bank_epilogue = "";  // filterbank stage (+ MFCC launch) of the last successful execute (sgx_bank_stage_name): "" before any / without a bank
+    mutable std::string bank_stage_text;               // the two put together for the caller
     const char *istft_route = "";  // route of the last successful sgx_istft / sgx_c2r (sgx_istft_kernel_name): "" before any
     // K_BIGFFT: tables of the global-memory transforms and their sequence scratch (grown on demand, pre-sized by sgx_reserve)
     sgx::BigDev big;

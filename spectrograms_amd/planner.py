@@ -272,6 +272,11 @@ class Plan:
         """Route of the last successful istft_batch / istft / c2r call (sgx_istft_kernel_name); "" before any."""
         return self._lib.sgx_istft_kernel_name(self._h).decode()
 
+    @property
+    def bank_stage_name(self) -> str:
+        """Filterbank stage of the last successful compute call (sgx_bank_stage_name); "" before any and for plans without a bank."""
+        return self._lib.sgx_bank_stage_name(self._h).decode()
+
     def output_shape(self, signal_length: int) -> Tuple[int, int]:
         if int(signal_length) <= 0:
             raise ValueError("signal_length must be > 0")

@@ -70,6 +70,49 @@ def np_mel_filterbank(sr, n_fft, n_mels, f_min, f_max, norm=None):
     return fb
 
 
+def np_loghz(sr, n_fft, n_bins, f_min, f_max):
+    nb = n_fft // 2 + 1
+    freqs = np.exp(np.log(f_min) + np.arange(n_bins) * (np.log(f_max) - np.log(f_min)) / (n_bins - 1))
+    m = np.zeros((n_bins, nb))
+    for b, f in enumerate(freqs):
+        e = f / (sr / n_fft)
+        lo, hi = int(np.floor(e)), min(int(np.ceil(e)), nb - 1)
+        if lo >= nb:
+            continue
+        if lo == hi:
+            m[b, lo] = 1.0
+        else:
+            m[b, lo] = 1.0 - (e - lo)
+            m[b, hi] = e - lo
+    m[np.abs(m) <= 1e-10] = 0.0
+    return m, freqs
+
+
+def np_chroma_bank(sr, n_fft, tuning=440.0, f_min=32.7, f_max=4186.0):
+    freqs = np.arange(n_fft // 2 + 1) * sr / n_fft
+    fb = np.zeros((12, freqs.size))
+    ok = (freqs >= f_min) & (freqs <= f_max) & (freqs > 0)
+    pc = np.mod(69.0 + 12.0 * np.log2(freqs[ok] / tuning), 12.0)
+    d = np.abs(pc[None, :] - np.arange(12.0)[:, None])
+    fb[:, ok] = np.exp(-0.5 * np.minimum(d, 12.0 - d) ** 2)
+    s = fb.sum(axis=1, keepdims=True)
+    return np.where(s > 0, fb / np.where(s > 0, s, 1.0), fb)
+
+
+def np_erb(sr, n_fft, n_filters, f_min, f_max, spacing=0):
+    if spacing == 0:
+        e = lambda f: 24.7 * (4.37 * f / 1000.0 + 1.0)
+        cf = (np.linspace(e(f_min), e(f_max), n_filters) / 24.7 - 1.0) * 1000.0 / 4.37
+    else:
+        shift = 9.26449 * 24.7
+        i = np.arange(1, n_filters + 1)
+        cf = (-shift + np.exp(i * (np.log(f_min + shift) - np.log(f_max + shift)) / n_filters) * (f_max + shift))[::-1]
+    freqs = np.arange(n_fft // 2 + 1) * sr / n_fft
+    bw = 1.019 * 24.7 * (4.37 * cf / 1000.0 + 1.0)
+    x = (freqs[None, :] - cf[:, None]) / bw[:, None]
+    return 1.0 / (1.0 + x * x) ** 4, cf
+
+
 def rel_err(a, b):
     """max |a-b| / max |b| (scale-relative error)."""
     a = np.asarray(a)

@@ -13,15 +13,7 @@ def sine(freq, sr=16000.0, n=16000):
     return np.sin(2.0 * np.pi * freq * np.arange(n) / sr)
 
 
-def np_chroma_bank(sr, n_fft, tuning=440.0, f_min=32.7, f_max=4186.0):
-    freqs = np.arange(n_fft // 2 + 1) * sr / n_fft
-    fb = np.zeros((12, freqs.size))
-    ok = (freqs >= f_min) & (freqs <= f_max) & (freqs > 0)
-    pc = np.mod(69.0 + 12.0 * np.log2(freqs[ok] / tuning), 12.0)
-    d = np.abs(pc[None, :] - np.arange(12.0)[:, None])
-    fb[:, ok] = np.exp(-0.5 * np.minimum(d, 12.0 - d) ** 2)
-    s = fb.sum(axis=1, keepdims=True)
-    return np.where(s > 0, fb / np.where(s > 0, s, 1.0), fb)
+np_chroma_bank = H.np_chroma_bank  # (the NumPy restatement lives in tests/helpers.py, shared with test_bank_readback.py)
 
 
 @pytest.mark.parametrize("norm", ["none", "l1", "l2", "max"])

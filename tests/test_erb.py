@@ -11,18 +11,7 @@ from spectrograms_amd import _ffi
 from tests import helpers as H
 
 
-def np_erb(sr, n_fft, n_filters, f_min, f_max, spacing=0):
-    if spacing == 0:
-        e = lambda f: 24.7 * (4.37 * f / 1000.0 + 1.0)
-        cf = (np.linspace(e(f_min), e(f_max), n_filters) / 24.7 - 1.0) * 1000.0 / 4.37
-    else:
-        shift = 9.26449 * 24.7
-        i = np.arange(1, n_filters + 1)
-        cf = (-shift + np.exp(i * (np.log(f_min + shift) - np.log(f_max + shift)) / n_filters) * (f_max + shift))[::-1]
-    freqs = np.arange(n_fft // 2 + 1) * sr / n_fft
-    bw = 1.019 * 24.7 * (4.37 * cf / 1000.0 + 1.0)
-    x = (freqs[None, :] - cf[:, None]) / bw[:, None]
-    return 1.0 / (1.0 + x * x) ** 4, cf
+np_erb = H.np_erb  # (the NumPy restatement lives in tests/helpers.py, shared with test_bank_readback.py)
 
 
 @pytest.mark.parametrize("spacing", [0, 1])

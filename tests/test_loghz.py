@@ -11,22 +11,7 @@ from spectrograms_amd import _ffi
 from tests import helpers as H
 
 
-def np_loghz(sr, n_fft, n_bins, f_min, f_max):
-    nb = n_fft // 2 + 1
-    freqs = np.exp(np.log(f_min) + np.arange(n_bins) * (np.log(f_max) - np.log(f_min)) / (n_bins - 1))
-    m = np.zeros((n_bins, nb))
-    for b, f in enumerate(freqs):
-        e = f / (sr / n_fft)
-        lo, hi = int(np.floor(e)), min(int(np.ceil(e)), nb - 1)
-        if lo >= nb:
-            continue
-        if lo == hi:
-            m[b, lo] = 1.0
-        else:
-            m[b, lo] = 1.0 - (e - lo)
-            m[b, hi] = e - lo
-    m[np.abs(m) <= 1e-10] = 0.0
-    return m, freqs
+np_loghz = H.np_loghz  # (the NumPy restatement lives in tests/helpers.py, shared with test_bank_readback.py)
 
 
 @pytest.mark.parametrize("n_fft,hop,n_bins,fmin,fmax", [(512, 256, 128, 20.0, 8000.0), (1024, 256, 64, 50.0, 7000.0), (400, 160, 40, 100.0, 4000.0)])
