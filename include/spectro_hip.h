@@ -418,6 +418,46 @@ const char *sgx_binaural_kernel_name(const sgx_binaural *plan);
 int32_t sgx_binaural_device(const sgx_binaural *plan);
 const char *sgx_binaural_last_error(const sgx_binaural *plan); /* NULL plan: the text of the last failed create */
 
+/* ---- gammatone IIR plans: gammatone_iir_spectrogram / gammatone_center_frequencies (src/erb.rs:405-654), batched.  The time-domain
+ * filter bank the reference offers beside the frequency-domain ErbFilterbank of the SGX_FREQ_ERB plans: no FFT, every (signal, frame,
+ * band) is an 8th-order recurrence in f64 from zero state.
+ *   centre frequencies cf[band], low to high: those of the SGX_FREQ_ERB plans for the same n_filters, f_min, f_max, erb_spacing
+ *   per band, Ts = 1 / sample_rate, B = 1.019 2 pi (cf / 9.26449 + 24.7), th = 2 pi cf Ts, E = exp(-B Ts): four sections
+ *     y = a0_k x + z0;  z0 = a1_k x + z1 - b1 y;  z1 = -b2 y      (Direct Form II transposed, a2 = 0, z0 = z1 = 0 at the frame's start)
+ *     b1 = -2 cos(th) E, b2 = exp(-2 B Ts), a0_k = Ts, a1_k = -E (Ts cos(th) +- s Ts sin(th)) with +s2, -s2, +s1, -s1 for k = 1..4,
+ *     s1 = sqrt(3 - 2 sqrt 2), s2 = sqrt(3 + 2 sqrt 2); a0_1 and a1_1 divided by the gain of iir_gain (:426-453)
+ *   frames: no centring, no padding, n_frames = 1 + (n_samples - frame_size) / hop_size; frame f = samples [f hop, f hop + frame_size) as
+ *     f64 times w[i] = 0.5 - 0.5 cos(2 pi i / (frame_size - 1))
+ *   out[band][f] = T(sqrt(sum(y4^2) / frame_size)), the arithmetic in f64 for both T; with a dB floor, in T:
+ *     v > eps ? 10 log10(v) : 10 log10(eps), eps = T(10^(db_floor / 10)) (a NaN value takes the floor, as T::max ignores it); the second
+ *     value is computed once on the host.
+ * Errors: sample_rate <= 0 "sample_rate must be > 0"; fewer than frame_size samples "signal is shorter than frame_size" (both
+ * SGX_INVALID_INPUT, texts of the reference); the ErbParams::new checks on n_filters, f_min, f_max with their texts.  Refused where the
+ * reference divides by zero or loops: frame_size < 2, hop_size == 0, a non-finite sample_rate or db_floor.  f_max above Nyquist is
+ * accepted, as in the reference (the poles stay inside the unit circle).  Limits of the launch: n_filters <= 65536, frame_size and
+ * hop_size below 2^31.  device -1: the current device, -2: a host-only plan (validation, shapes, centre frequencies, coefficients, route;
+ * the compute calls return SGX_BACKEND). */
+typedef struct sgx_gammatone sgx_gammatone; /* opaque; same single-caller rule as sgx_mdct */
+#define SGX_GAMMATONE_COEFFS 11 /* doubles per band of sgx_gammatone_coefficients */
+sgx_status sgx_gammatone_create(double sample_rate, size_t frame_size, size_t hop_size, uint32_t n_filters, double f_min, double f_max,
+                                int32_t erb_spacing, int32_t has_db_floor, double db_floor, int32_t dtype, int32_t device,
+                                sgx_gammatone **out);
+void sgx_gammatone_destroy(sgx_gammatone *plan);
+sgx_status sgx_gammatone_output_shape(const sgx_gammatone *plan, size_t n_samples, size_t *n_bands, size_t *n_frames);
+/* `batch` signals: row r at samples + r * sample_stride (elements of T, sample_stride >= n_samples), n_samples each;
+ * out [batch][n_bands][n_frames] T.  out_elems must be that count (else SGX_DIM_MISMATCH); mem_kind and hip_stream as sgx_execute. */
+sgx_status sgx_gammatone_execute(sgx_gammatone *plan, const void *samples, size_t batch, size_t n_samples, size_t sample_stride, void *out,
+                                 size_t out_elems, int32_t mem_kind, void *hip_stream);
+sgx_status sgx_gammatone_center_frequencies(const sgx_gammatone *plan, double *out /* n_filters */);
+/* The coefficients as built (f64) and as the kernel reads them, per band: a0_1, a1_1 (both already divided by the gain), a0_2, a1_2,
+ * a0_3, a1_3, a0_4, a1_4, b1, b2, gain. */
+sgx_status sgx_gammatone_coefficients(const sgx_gammatone *plan, double *out /* [n_filters][SGX_GAMMATONE_COEFFS] */);
+/* Pre-sizes the SGX_MEM_HOST staging for calls of up to `batch` signals of `n_samples` samples (the kernel itself needs no scratch). */
+sgx_status sgx_gammatone_reserve(sgx_gammatone *plan, size_t batch, size_t n_samples, int32_t host_staging);
+const char *sgx_gammatone_kernel_name(const sgx_gammatone *plan); /* "k_gammatone_iir": one kernel for every shape and both types */
+int32_t sgx_gammatone_device(const sgx_gammatone *plan);
+const char *sgx_gammatone_last_error(const sgx_gammatone *plan); /* NULL plan: the text of the last failed create */
+
 #ifdef __cplusplus
 }
 #endif

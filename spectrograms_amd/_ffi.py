@@ -36,6 +36,8 @@ SYMBOLS = [
     "sgx_mdct_reserve", "sgx_mdct_window", "sgx_mdct_kernel_name", "sgx_mdct_device", "sgx_mdct_last_error",
     "sgx_binaural_create", "sgx_binaural_destroy", "sgx_binaural_output_shape", "sgx_binaural_axes", "sgx_binaural_execute",
     "sgx_binaural_histogram", "sgx_binaural_reserve", "sgx_binaural_kernel_name", "sgx_binaural_device", "sgx_binaural_last_error",
+    "sgx_gammatone_create", "sgx_gammatone_destroy", "sgx_gammatone_output_shape", "sgx_gammatone_execute", "sgx_gammatone_center_frequencies",
+    "sgx_gammatone_coefficients", "sgx_gammatone_reserve", "sgx_gammatone_kernel_name", "sgx_gammatone_device", "sgx_gammatone_last_error",
 ]
 
 
@@ -206,6 +208,21 @@ def lib() -> C.CDLL:
     L.sgx_binaural_device.restype = C.c_int32
     L.sgx_binaural_last_error.argtypes = [vp]
     L.sgx_binaural_last_error.restype = C.c_char_p
+    L.sgx_gammatone_create.argtypes = [C.c_double, sz, sz, C.c_uint32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                       C.c_int32, C.POINTER(vp)]
+    L.sgx_gammatone_destroy.argtypes = [vp]
+    L.sgx_gammatone_destroy.restype = None
+    L.sgx_gammatone_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.sgx_gammatone_execute.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_gammatone_center_frequencies.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_gammatone_coefficients.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_gammatone_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_gammatone_kernel_name.argtypes = [vp]
+    L.sgx_gammatone_kernel_name.restype = C.c_char_p
+    L.sgx_gammatone_device.argtypes = [vp]
+    L.sgx_gammatone_device.restype = C.c_int32
+    L.sgx_gammatone_last_error.argtypes = [vp]
+    L.sgx_gammatone_last_error.restype = C.c_char_p
     _lib = L
     return L
 

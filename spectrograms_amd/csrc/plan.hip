@@ -233,17 +233,7 @@ void build_loghz_csr(const sgx_params &p, std::vector<uint32_t> &ptr, std::vecto
 void build_erb_dense(const sgx_params &p, std::vector<uint32_t> &ptr, std::vector<uint32_t> &col, std::vector<double> &val,
                      std::vector<double> &centres) {
     const size_t nf = p.n_mels, nb = p.n_fft / 2 + 1;
-    centres.resize(nf);
-    if (p.erb_spacing == SGX_ERB_APPLE_TR35) {  // apple_tr35_center_freqs :221-238 (computed high->low, stored low->high)
-        const double shift = 9.26449 * 24.7;
-        const double d = p.f_max + shift;
-        const double e = (std::log(p.f_min + shift) - std::log(p.f_max + shift)) / double(nf);
-        for (size_t i = 0; i < nf; ++i) centres[nf - 1 - i] = -shift + std::exp((double(i) + 1.0) * e) * d;
-    } else {  // uniform on hz_to_erb :208-210, back through erb_to_hz :249-251
-        const double lo = 24.7 * (4.37 * p.f_min / 1000.0 + 1.0), hi = 24.7 * (4.37 * p.f_max / 1000.0 + 1.0);
-        const double step = (hi - lo) / double(nf - 1);
-        for (size_t i = 0; i < nf; ++i) centres[i] = (std::fma(double(i), step, lo) / 24.7 - 1.0) * 1000.0 / 4.37;
-    }
+    erb_center_freqs(nf, p.f_min, p.f_max, p.erb_spacing, centres);
     const double df = p.sample_rate_hz / double(p.n_fft);
     ptr.resize(nf + 1);
     col.resize(nf * nb);
@@ -2070,4 +2060,18 @@ namespace sgx {
 void note_bank_stage(const char *name) { (name[0] == '+' ? t_bank_epilogue : t_bank_stage) = name; }
 
 void make_window_f64(const sgx_params &p, const std::vector<double> &custom, std::vector<double> &w) { build_window(p, custom, w); }
+
+void erb_center_freqs(size_t nf, double f_min, double f_max, int spacing, std::vector<double> &centres) {
+    centres.resize(nf);
+    if (spacing == SGX_ERB_APPLE_TR35) {  // apple_tr35_center_freqs :221-238 (computed high->low, stored low->high)
+        const double shift = 9.26449 * 24.7;
+        const double d = f_max + shift;
+        const double e = (std::log(f_min + shift) - std::log(f_max + shift)) / double(nf);
+        for (size_t i = 0; i < nf; ++i) centres[nf - 1 - i] = -shift + std::exp((double(i) + 1.0) * e) * d;
+    } else {  // uniform on hz_to_erb :208-210, back through erb_to_hz :249-251
+        const double lo = 24.7 * (4.37 * f_min / 1000.0 + 1.0), hi = 24.7 * (4.37 * f_max / 1000.0 + 1.0);
+        const double step = (hi - lo) / double(nf - 1);
+        for (size_t i = 0; i < nf; ++i) centres[i] = (std::fma(double(i), step, lo) / 24.7 - 1.0) * 1000.0 / 4.37;
+    }
+}
 }  // namespace sgx

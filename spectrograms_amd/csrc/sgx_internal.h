@@ -312,6 +312,9 @@ hipError_t launch_cqt(const CqtArgs &a, unsigned lds_m, int dtype, hipStream_t s
 // make_window (src/spectrogram.rs:2159-2235) in f64 at length p.n_fft for p.window_kind / p.window_param (plan.hip build_window);
 // SGX_WIN_CUSTOM copies `custom`.  The MDCT plans (mdct.hip) build their analysis / synthesis window with it.
 void make_window_f64(const sgx_params &p, const std::vector<double> &custom, std::vector<double> &w);
+// ERB / gammatone centre frequencies, low to high, for spacing SGX_ERB_* (apple_tr35_center_freqs src/erb.rs:221-236, the uniform ERB
+// scale :592-598): the axis of the ERB spectrogram plans' bank (plan.hip build_erb_dense) and of the gammatone IIR plans (gammatone.hip)
+void erb_center_freqs(size_t n_filters, double f_min, double f_max, int spacing, std::vector<double> &centres);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: remember which (kernel, device) pairs have been
 // configured, so a process that drives several GPUs (sgx_params.device) gets the large-LDS opt-in on each of them.

@@ -209,9 +209,11 @@ class ErbParams:
     """ErbParams(n_filters, f_min, f_max) — src/erb.rs:27-92, Python class src/python/params.rs:910-980.
 
     `spacing`: "linear" (uniform on the Glasberg & Moore ERB scale, default) or "apple_tr35" (ErbSpacing, erb.rs:14-25).
+    `db_floor` (erb.rs:39-42, set through `with_db_floor`): read by the gammatone IIR plans only, which then return dB with that floor;
+    the ERB spectrogram plans ignore it, as the reference's do.
     """
 
-    def __init__(self, n_filters: int, f_min: float, f_max: float, spacing: str = "linear"):
+    def __init__(self, n_filters: int, f_min: float, f_max: float, spacing: str = "linear", db_floor: Optional[float] = None):
         if int(n_filters) < 2:
             raise _ffi.InvalidInputError("Invalid input: n_filters must be >= 2 (single filter would cause division by zero)")
         if f_min < 0.0 or math.isinf(f_min):
@@ -221,9 +223,13 @@ class ErbParams:
         if spacing not in ("linear", "apple_tr35"):
             raise ValueError("spacing must be 'linear' or 'apple_tr35'")
         self.n_filters, self.f_min, self.f_max, self.spacing = int(n_filters), float(f_min), float(f_max), spacing
+        self.db_floor = None if db_floor is None else float(db_floor)
 
     def with_spacing(self, spacing: str) -> "ErbParams":
-        return ErbParams(self.n_filters, self.f_min, self.f_max, spacing)
+        return ErbParams(self.n_filters, self.f_min, self.f_max, spacing, self.db_floor)
+
+    def with_db_floor(self, floor_db: float) -> "ErbParams":  # erb.rs:102-107
+        return ErbParams(self.n_filters, self.f_min, self.f_max, self.spacing, float(floor_db))
 
     @staticmethod
     def speech_standard() -> "ErbParams":  # erb.rs:170-173
