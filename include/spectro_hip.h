@@ -31,6 +31,18 @@
  *    call's size (host staging, the MFCC Mel tensor, the generic inverse path's
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
+ *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
+ *    _histogram, sgx_gammatone_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
+ *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
+ *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
+ *    on one plan that go to different streams must be ordered by the caller (events), as must a host-pointer call behind a
+ *    device-pointer call still in flight.  A call does not depend on the calls before it: a larger, smaller, failed, host- or
+ *    device-pointer call in between changes neither the bits nor the route of the next one (the DC / Nyquist flag word is
+ *    cleared per call).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
+ *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
+ *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
+ *    by tests/test_stream_order.py.
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H
