@@ -29,6 +29,7 @@
 
 using namespace sgx;
 
+constexpr char kNfftTooLarge[] = "hip -- FFT backend error: n_fft too large (the global-memory transforms take n_fft up to 2^20, powers of two up to 2^21)";
 constexpr unsigned kBigMin = 2048;  // frame lengths above this never run an O(n^2) kernel: bigfft.hip takes what has no O(n log n) kernel on chip
 
 #ifndef SGX_BANDPF
@@ -443,7 +444,48 @@ sgx_status upload_cast(sgx_plan *pl, void **dst, const std::vector<double> &src)
     return upload<T>(pl, dst, tmp);
 }
 
-sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need);
+template <typename T>
+sgx_status upload_bs(sgx_plan *pl, BsDevTables &d, const BsHostTables &h) {  // chirp-z tables of bluestein_host_tables
+    sgx_status st;
+    if ((st = upload_cast<T>(pl, &d.chirp, h.chirp)) != SGX_OK) return st;
+    if ((st = upload_cast<T>(pl, &d.bhp, h.bhp)) != SGX_OK) return st;
+    if ((st = upload_cast<T>(pl, &d.tw, h.tw)) != SGX_OK) return st;
+    d.M = h.M;
+    return SGX_OK;
+}
+
+sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need) {
+    if (*have >= need) return SGX_OK;
+    if (*buf) SGX_HIP(pl, hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    SGX_HIP(pl, hipMalloc(buf, need));
+    *have = need;
+    return SGX_OK;
+}
+
+// W_N^p (sign2 = -2.0) or its conjugate (+2.0) as (cos, sin) in T.  The angle is formed in this order and no other: the integer
+// exponent converted to f64, times sign2 * pi, divided by N; cos and sin in f64; one cast to T.  A reassociated form (p times a
+// precomputed 2 pi / N, say) moves last bits of the f32 twiddles, and with them every stored output of the kernels that read them.
+template <typename T>
+void put_twiddle(T *at, double sign2, unsigned p, unsigned N) {
+    const double a = sign2 * kPi * double(p) / double(N);
+    at[0] = T(std::cos(a));
+    at[1] = T(std::sin(a));
+}
+template <typename T>
+std::vector<T> twiddle_vector(unsigned count, double sign2, unsigned N) {  // [k] = W_N^(+-k), k < count
+    std::vector<T> t(2 * size_t(count));
+    for (unsigned k = 0; k < count; ++k) put_twiddle(&t[2 * size_t(k)], sign2, k, N);
+    return t;
+}
+template <typename T>
+std::vector<T> twiddle_grid(unsigned rows, unsigned cols) {  // [r][c] = W_N^(r c), N = rows cols: the twiddles between the two passes
+    std::vector<T> t(2 * size_t(rows) * cols);
+    for (unsigned r = 0; r < rows; ++r)
+        for (unsigned c = 0; c < cols; ++c) put_twiddle(&t[2 * (size_t(r) * cols + c)], -2.0, r * c, rows * cols);
+    return t;
+}
 
 // Device layout of a CQT plan (sgx_internal.h CqtArgs, cqt.hip): bins in ascending order in groups of 8, group g a dense [L_g][16]
 // block of T (column 2c = Re K, 2c + 1 = -Im K of bin 8 g + c, right-aligned: block row j is frame tap n_fft - L_g + j, zero in
@@ -498,21 +540,110 @@ sgx_status cqt_device_tables(sgx_plan *pl) {
     return upload<uint32_t>(pl, &pl->d_cqt_len, pl->cqt_len);
 }
 
+// The shape-specific kernels at the head of the chain, one entry each: all the host code knows about them.  Plan creation starts
+// on the entry whose dtype and `selects` match, and everything else looks the plan's kind up here.
+//   schedule : build_band_schedule's waves, segments, word limit and read-ahead segments (a weight is one word in f32, two in f64)
+//   tw1      : [tw1_rows][tw1_cols] grid W_N^(k1 n2), N = tw1_rows tw1_cols, between the two passes of the N-point complex transform
+//   tw2      : the real split of the 2 N-point transform, entries W' = -i W_2N^k = (sin a, -cos a):
+//              TW2_LANES  [tw2_rows][tw2_cols], k = kb + tw2_rows u: the pair (Z[k], Z[N - k]) a lane of kind kb splits u-th
+//              TW2_JOBS   float4 (W', W'^perp) = (wi, -wr, wr, wi) [tw2_rows jobs][16] at row stride 17 in each job's consumption order
+//                         (r32x16_layout.h): job j splits (Z[k], Z[N - k]) with k = c1 + 2 tw2_rows i (i < 8) or c2 + 2 tw2_rows (i - 8),
+//                         c1 = j, c2 = j + N / 2, but job 0: c1 = tw2_job0[0], c2 = tw2_job0[1]
+//   window   : 0.5 * window (exact) and a vector of 0.5 for sgx_r2c, of window_len entries (0: n_fft); a shorter window is stored
+//              with each coefficient repeated (n_fft 512 on k_r32x16, two frames per transform: the pair (w[i], w[i]) multiplies
+//              z[i] = a[i] + i b[i])
+enum Tw2Form { TW2_NONE, TW2_LANES, TW2_JOBS };
+struct TunedKernel {
+    KernelKind kind;
+    const char *name;  // sgx_kernel_name
+    int dtype;
+    bool (*selects)(const sgx_params &p);
+    bool (*geometry)(StftArgs &a);
+    hipError_t (*launch)(const StftArgs &a, hipStream_t s);
+    unsigned sched_waves, sched_segs, sched_max_words, sched_ahead;
+    unsigned tw1_rows, tw1_cols;
+    Tw2Form tw2;
+    unsigned tw2_rows, tw2_cols, tw2_job0[2];
+    unsigned window_len;
+};
+const TunedKernel kTuned[] = {
+    // n_fft 1024; n_fft 512 (two frames per transform): staged variants at hops 64 / 128 / 160 / 256, the packed form's per-lane loads at
+    // every other even hop (per-bin outputs; else falls back).  4 waves and one more, empty, segment of records behind the last:
+    // k_r32x16 fetches a record ahead unconditionally
+    {K_R32X16_F32, "r32x16_f32", SGX_F32,
+     [](const sgx_params &p) { return (p.n_fft == 1024 && (SGX_ODDHOP || p.hop_size % 2 == 0)) || (p.n_fft == 512 && p.hop_size % 2 == 0 && p.hop_size <= 512); },
+     plan_geometry_r32x16_f32, launch_r32x16_f32, 4, r32x16::kSchedSegs, r32x16::kMelMaxWords, 1, 32, 16, TW2_JOBS, 16, 16, {16, 0}, 1024},
+    // n_fft 2048 (odd hops: register-tiled kernel)
+    {K_R32X32_F32, "r32x32_f32", SGX_F32, [](const sgx_params &p) { return p.n_fft == 2048; },
+     plan_geometry_r32x32_f32, launch_r32x32_f32, 8, r32x32::kSegs2, r32x32::kSch2MaxWords, 0, 32, 32, TW2_JOBS, 32, 16, {0, 32}, 0},
+    // f64 n_fft 1024, per-bin and complex outputs (filterbanks, odd hops: register-tiled kernel)
+    {K_D32X16_F64, "d32x16_f64", SGX_F64, [](const sgx_params &p) { return p.n_fft == 1024; },
+     plan_geometry_d32x16_f64, launch_d32x16_f64, 8, d32x16::kDSegs, d32x16::kDSchMaxWords, 0, 16, 32, TW2_LANES, 32, 8, {}, 0},
+    // f64 n_fft 512, two frames per transform: the 512-point complex transform of a frame pair, no real split (kernels_d32x16.hip k_d512)
+    {K_D512_F64, "d512_f64", SGX_F64, [](const sgx_params &p) { return p.n_fft == 512 && p.hop_size <= 260; },
+     plan_geometry_d512_f64, launch_d512_f64, 8, d512::kSegs, d512::kSchMaxWords, 0, 16, 32, TW2_NONE, 0, 0, {}, 0},
+    // f32 n_fft 4096, per-bin and complex outputs; filterbanks: split path.  The schedule as k_d32x32's, 4-byte weights (kernels_r64x32.hip)
+    {K_R64X32_F32, "r64x32_f32", SGX_F32, [](const sgx_params &p) { return p.n_fft == 4096; },
+     plan_geometry_r64x32_f32, launch_r64x32_f32, 16, 2, 1u << 20, 0, 32, 64, TW2_LANES, 64, 16, {}, 0},
+    // f64 n_fft 2048, per-bin and complex outputs.  16 half-waves x 8 slots; the schedule stays in global memory (kernels_d32x32.hip)
+    {K_D32X32_F64, "d32x32_f64", SGX_F64, [](const sgx_params &p) { return p.n_fft == 2048; },
+     plan_geometry_d32x32_f64, launch_d32x32_f64, 16, 2, 1u << 20, 0, 32, 32, TW2_LANES, 64, 8, {}, 0},
+};
+const TunedKernel *tuned_kernel(KernelKind k) {
+    for (const TunedKernel &t : kTuned)
+        if (t.kind == k) return &t;
+    return nullptr;
+}
+bool kind_is_tuned(KernelKind k) { return tuned_kernel(k) != nullptr; }
+
+// tw1, tw2 and the half window of a plan on tuned kernel `k` (the layouts: beside kTuned)
+template <typename T>
+sgx_status tuned_tables(sgx_plan *pl, const TunedKernel &k) {
+    const unsigned n = pl->p.n_fft, N = k.tw1_rows * k.tw1_cols;
+    sgx_status st;
+    if ((st = upload<T>(pl, &pl->d_tw1, twiddle_grid<T>(k.tw1_rows, k.tw1_cols))) != SGX_OK) return st;
+    std::vector<T> t2;
+    if (k.tw2 == TW2_LANES) {
+        t2.resize(2 * size_t(k.tw2_rows) * k.tw2_cols);
+        for (unsigned kb = 0; kb < k.tw2_rows; ++kb)
+            for (unsigned u = 0; u < k.tw2_cols; ++u) {
+                T w[2], *q = &t2[2 * (size_t(kb) * k.tw2_cols + u)];
+                put_twiddle(w, -2.0, kb + k.tw2_rows * u, 2 * N);
+                q[0] = w[1]; q[1] = -w[0];  // W' = -i (wr + i wi) = (wi, -wr)
+            }
+    }
+    if (k.tw2 == TW2_JOBS) {
+        t2.assign(size_t(k.tw2_rows) * 17 * 4, T(0));
+        for (unsigned j = 0; j < k.tw2_rows; ++j)
+            for (unsigned i = 0; i < 16; ++i) {
+                const unsigned c1 = j == 0 ? k.tw2_job0[0] : j, c2 = j == 0 ? k.tw2_job0[1] : j + N / 2;
+                T w[2], *q = &t2[4 * (size_t(j) * 17 + i)];  // with W = (wr, wi): W' = -i W and W'^perp = (-W'.y, W'.x) = (wr, wi), T = D.x W' + D.y W'^perp
+                put_twiddle(w, -2.0, i < 8 ? c1 + 2 * k.tw2_rows * i : c2 + 2 * k.tw2_rows * (i - 8), 2 * N);
+                q[0] = w[1]; q[1] = -w[0]; q[2] = w[0]; q[3] = w[1];
+            }
+    }
+    if ((st = upload<T>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
+    const unsigned reps = k.window_len ? k.window_len / n : 1u;
+    std::vector<T> wh(size_t(n) * reps), oh(size_t(n) * reps, T(0.5));
+    for (size_t i = 0; i < wh.size(); ++i) wh[i] = T(0.5) * T(pl->window[i / reps]);  // exact scaling of the window in T
+    if ((st = upload<T>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
+    return upload<T>(pl, &pl->d_ones_half, oh);
+}
+
 // Band schedule of the tuned f32 kernel (n_fft 1024, and 512 in its two-frames-per-transform mode), built on the HOST at plan
 // creation — before the kernel kind is resolved, so that a bank without a schedule (rows that are not runs of bins, too many
 // words) resolves to the kernel that will really run it, and the split-filterbank decision is made for that kernel.
 // A padding step has weight +0: it adds +0 to the running sum as long as |X|^2 of that bin is finite.  A non-finite |X|^2
 // (possible only with non-finite or > 1e19 samples, which poison the whole frame's spectrum anyway) within the padded cover
 // of a band — up to 11 bins past its last — makes that band NaN where the reference's CSR sum would not look at the bin.
-// (NW waves; `ahead` = 1: one more, empty, segment of records behind the last — k_r32x16 fetches a record ahead unconditionally)
-void build_band_schedule(sgx_plan *pl, unsigned NW = 4, unsigned kSegs = r32x16::kSchedSegs, unsigned max_words = r32x16::kMelMaxWords, unsigned ahead = 1,
-                         unsigned wwords = 1 /* 32-bit words per weight: 1 = f32, 2 = f64 (k_d32x16) */) {
+// (the schedule parameters of kernel `k`: NW waves; `ahead` more, empty, segments of records behind the last)
+void build_band_schedule(sgx_plan *pl, const TunedKernel &k) {
+    const unsigned NW = k.sched_waves, kSegs = k.sched_segs, max_words = k.sched_max_words, ahead = k.sched_ahead;
+    const unsigned wwords = k.dtype == SGX_F64 ? 2 : 1;  // 32-bit words per weight
     pl->h_mel_sched.clear();
     pl->mel_sched_words = 0;
     if (pl->out_mode != OUT_MEL || pl->mel_ptr.size() != size_t(pl->p.n_mels) + 1) return;
-    for (size_t m = 0; m < pl->p.n_mels; ++m)
-        for (uint32_t i = pl->mel_ptr[m]; i + 1 < pl->mel_ptr[m + 1]; ++i)
-            if (pl->mel_col[i + 1] != pl->mel_col[i] + 1) return;  // rows must be runs of consecutive bins
+    if (!pl->mel_contig) return;  // rows must be runs of consecutive bins
     if (wwords == 1 && pl->p.n_fft == 1024 && pl->mel_val.size() >= size_t(48) * pl->p.n_mels) return;  // f32, wide rows: matrix-core epilogue
     {
         const unsigned nm = pl->p.n_mels;
@@ -612,25 +743,14 @@ sgx_status build_device_tables(sgx_plan *pl) {
     const unsigned n = pl->p.n_fft;
     sgx_status st;
     if ((st = upload_cast<T>(pl, &pl->d_window, pl->window)) != SGX_OK) return st;
-    std::vector<T> tw(2 * size_t(n));
-    for (unsigned k = 0; k < n; ++k) {  // tw[k] = exp(-2 pi i k / n), evaluated in f64
-        const double a = -2.0 * kPi * double(k) / double(n);
-        tw[2 * k] = T(std::cos(a));
-        tw[2 * k + 1] = T(std::sin(a));
-    }
-    if ((st = upload<T>(pl, &pl->d_tw, tw)) != SGX_OK) return st;
+    if ((st = upload<T>(pl, &pl->d_tw, twiddle_vector<T>(n, -2.0, n))) != SGX_OK) return st;  // tw[k] = exp(-2 pi i k / n)
     if (pl->out_mode == OUT_MEL) {
         if ((st = upload<uint32_t>(pl, &pl->d_mel_ptr, pl->mel_ptr)) != SGX_OK) return st;
         if ((st = upload<uint32_t>(pl, &pl->d_mel_col, pl->mel_col)) != SGX_OK) return st;
         if ((st = upload_cast<T>(pl, &pl->d_mel_val, pl->mel_val)) != SGX_OK) return st;
         // triangular bands are contiguous column runs; build a 4-wide padded copy (4-element
         // aligned column groups, zero weights outside the true band) so the reduction reads LDS 16 bytes at a time
-        bool contig = true;
-        for (size_t m = 0; m < pl->p.n_mels && contig; ++m)
-            for (uint32_t i = pl->mel_ptr[m]; i + 1 < pl->mel_ptr[m + 1]; ++i)
-                contig = contig && (pl->mel_col[i + 1] == pl->mel_col[i] + 1);
-        pl->mel_contig = contig ? 1u : 0u;
-        if (contig) {
+        if (pl->mel_contig) {
             std::vector<uint32_t> pptr(pl->p.n_mels + 1, 0), pcol(pl->p.n_mels, 0);
             std::vector<T> pw;
             for (size_t m = 0; m < pl->p.n_mels; ++m) {
@@ -703,8 +823,7 @@ sgx_status build_device_tables(sgx_plan *pl) {
             if ((st = upload<uint32_t>(pl, &pl->d_mm_blk, blk)) != SGX_OK) return st;
         }
         // Band schedule of the tuned kernel: built on the host at plan creation (build_band_schedule), uploaded here
-        if (((std::is_same<T, float>::value && (pl->kind == K_R32X16_F32 || pl->kind == K_R32X32_F32 || pl->kind == K_R64X32_F32)) || (std::is_same<T, double>::value && (pl->kind == K_D32X16_F64 || pl->kind == K_D512_F64 || pl->kind == K_D32X32_F64))) &&
-            !pl->h_mel_sched.empty() && !pl->d_mm_frag) {
+        if (kind_is_tuned(pl->kind) && !pl->h_mel_sched.empty() && !pl->d_mm_frag) {
             if ((st = upload<uint32_t>(pl, &pl->d_mel_sched, pl->h_mel_sched)) != SGX_OK) return st;
         }
     }
@@ -743,147 +862,8 @@ sgx_status build_device_tables(sgx_plan *pl) {
             }
         }
     }
-    if (pl->kind == K_R32X16_F32) {
-        // tw1[k1][n2] = W_512^(k1*n2) (pass-1 twiddles), tw2[j][k2] = W_1024^(j + 32*k2) (real-split twiddles)
-        // tw1[k1][n2] = W_512^(k1*n2); tw2[row][idx] = (wr, wi, wi, -wr) of W_1024^(row + 32*idx), row stride 17 float4
-        std::vector<float> t1(2 * 32 * 16), t2(16 * 17 * 4, 0.0f);
-        for (unsigned k1 = 0; k1 < 32; ++k1)
-            for (unsigned n2 = 0; n2 < 16; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 512.0;
-                t1[2 * (k1 * 16 + n2)] = float(std::cos(a));
-                t1[2 * (k1 * 16 + n2) + 1] = float(std::sin(a));
-            }
-        // tw2[job][i], i < 16: the pair the job splits i-th is (Z[k], Z[512 - k]) with k = c1 + 32 i (i < 8) or c2 + 32 (i - 8),
-        // c1 = j, c2 = j + 256 (job 0: 16 and 0).  With W = W_1024^k = (wr, wi) the kernel needs W' = -i W = (wi, -wr) and
-        // W'^perp = (-W'.y, W'.x) = (wr, wi):  T = D.x W' + D.y W'^perp.
-        for (unsigned j = 0; j < 16; ++j)
-            for (unsigned i = 0; i < 16; ++i) {
-                const unsigned c1 = j == 0 ? 16u : j, c2 = j == 0 ? 0u : j + 256u;
-                const unsigned k = i < 8 ? c1 + 32 * i : c2 + 32 * (i - 8);
-                const double a = -2.0 * kPi * double(k) / 1024.0;
-                const float wr = float(std::cos(a)), wi = float(std::sin(a));
-                float *q = &t2[4 * (j * 17 + i)];
-                q[0] = wi; q[1] = -wr; q[2] = wr; q[3] = wi;
-            }
-        if ((st = upload<float>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
-        std::vector<float> wh(1024), oh(1024, 0.5f);
-        if (n == 1024) {
-            for (unsigned i = 0; i < n; ++i) wh[i] = 0.5f * float(pl->window[i]);  // exact scaling of the f32 window
-        } else {  // n_fft 512, two frames per transform: the pair (w[i], w[i]) multiplies z[i] = a[i] + i b[i]
-            for (unsigned i = 0; i < 512; ++i) wh[2 * i] = wh[2 * i + 1] = 0.5f * float(pl->window[i]);
-        }
-        if ((st = upload<float>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
-    if (pl->kind == K_R32X32_F32) {
-        // tw1[k1][n2] = W_1024^(k1 n2), 32 x 32 (pass-1 twiddles); tw2[J][i], i < 16: the pair job J splits i-th is (Z[k], Z[1024 - k]) with
-        // k = c1 + 64 i (i < 8) or c2 + 64 (i - 8), c1 = J, c2 = J + 512 (job 0: 0 and 32); entry = (W', W'^perp), W' = -i W_2048^k
-        std::vector<float> t1(2 * 32 * 32), t2(32 * 17 * 4, 0.0f);
-        for (unsigned k1 = 0; k1 < 32; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 1024.0;
-                t1[2 * (k1 * 32 + n2)] = float(std::cos(a));
-                t1[2 * (k1 * 32 + n2) + 1] = float(std::sin(a));
-            }
-        for (unsigned J = 0; J < 32; ++J)
-            for (unsigned i = 0; i < 16; ++i) {
-                const unsigned c1 = J == 0 ? 0u : J, c2 = J == 0 ? 32u : J + 512u;
-                const unsigned k = i < 8 ? c1 + 64 * i : c2 + 64 * (i - 8);
-                const double a = -2.0 * kPi * double(k) / 2048.0;
-                const float wr = float(std::cos(a)), wi = float(std::sin(a));
-                float *q = &t2[4 * (J * 17 + i)];
-                q[0] = wi; q[1] = -wr; q[2] = wr; q[3] = wi;
-            }
-        if ((st = upload<float>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
-        std::vector<float> wh(2048), oh(2048, 0.5f);
-        for (unsigned i = 0; i < 2048; ++i) wh[i] = 0.5f * float(pl->window[i]);  // exact scaling of the f32 window
-        if ((st = upload<float>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
-    if (pl->kind == K_D32X16_F64) {
-        // tw1[k1][n2] = W_512^(k1 n2), 16 x 32 (pass-1 twiddles); tw2[kb][u] = W' = -i W_1024^(kb + 32 u): the pair (Z[k], Z[512 - k]) a lane of
-        // kind kb splits u-th (kernels_d32x16.hip)
-        std::vector<double> t1(2 * 16 * 32), t2(32 * 8 * 2);
-        for (unsigned k1 = 0; k1 < 16; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 512.0;
-                t1[2 * (k1 * 32 + n2)] = std::cos(a);
-                t1[2 * (k1 * 32 + n2) + 1] = std::sin(a);
-            }
-        for (unsigned kb = 0; kb < 32; ++kb)
-            for (unsigned u = 0; u < 8; ++u) {
-                const double a = -2.0 * kPi * double(kb + 32 * u) / 1024.0;
-                t2[2 * (kb * 8 + u)] = std::sin(a);       // W' = -i (wr + i wi) = (wi, -wr)
-                t2[2 * (kb * 8 + u) + 1] = -std::cos(a);
-            }
-        if ((st = upload<double>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
-        std::vector<double> wh(1024), oh(1024, 0.5);
-        for (unsigned i = 0; i < 1024; ++i) wh[i] = 0.5 * double(pl->window[i]);  // exact scaling
-        if ((st = upload<double>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
-    if (pl->kind == K_R64X32_F32) {
-        // tw1[k1][n2] = W_2048^(k1 n2), 32 x 64 (pass-1 twiddles); tw2[kb][u] = W' = -i W_4096^(kb + 64 u) (kernels_r64x32.hip); window w / 2
-        std::vector<float> t1(2 * 32 * 64), t2(2 * 64 * 16);
-        for (unsigned k1 = 0; k1 < 32; ++k1)
-            for (unsigned n2 = 0; n2 < 64; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 2048.0;
-                t1[2 * (k1 * 64 + n2)] = float(std::cos(a));
-                t1[2 * (k1 * 64 + n2) + 1] = float(std::sin(a));
-            }
-        for (unsigned kb = 0; kb < 64; ++kb)
-            for (unsigned u = 0; u < 16; ++u) {
-                const double a = -2.0 * kPi * double(kb + 64 * u) / 4096.0;
-                t2[2 * (kb * 16 + u)] = float(std::sin(a));       // W' = -i (wr + i wi) = (wi, -wr)
-                t2[2 * (kb * 16 + u) + 1] = float(-std::cos(a));
-            }
-        if ((st = upload<float>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
-        std::vector<float> wh(4096), oh(4096, 0.5f);
-        for (unsigned i = 0; i < 4096; ++i) wh[i] = 0.5f * float(pl->window[i]);  // exact scaling of the f32 window
-        if ((st = upload<float>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
-    if (pl->kind == K_D32X32_F64) {
-        // tw1[k1][n2] = W_1024^(k1 n2), 32 x 32 (pass-1 twiddles); tw2[kb][u] = W' = -i W_2048^(kb + 64 u) (kernels_d32x32.hip); window w / 2
-        std::vector<double> t1(2 * 32 * 32), t2(2 * 64 * 8);
-        for (unsigned k1 = 0; k1 < 32; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 1024.0;
-                t1[2 * (k1 * 32 + n2)] = std::cos(a);
-                t1[2 * (k1 * 32 + n2) + 1] = std::sin(a);
-            }
-        for (unsigned kb = 0; kb < 64; ++kb)
-            for (unsigned u = 0; u < 8; ++u) {
-                const double a = -2.0 * kPi * double(kb + 64 * u) / 2048.0;
-                t2[2 * (kb * 8 + u)] = std::sin(a);       // W' = -i (wr + i wi) = (wi, -wr)
-                t2[2 * (kb * 8 + u) + 1] = -std::cos(a);
-            }
-        if ((st = upload<double>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
-        std::vector<double> wh(2048), oh(2048, 0.5);
-        for (unsigned i = 0; i < 2048; ++i) wh[i] = 0.5 * double(pl->window[i]);
-        if ((st = upload<double>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
-    if (pl->kind == K_D512_F64) {
-        // tw1[k1][n2] = W_512^(k1 n2), 16 x 32 (the 512-point complex transform of a frame pair: kernels_d32x16.hip k_d512); window w[n] / 2
-        std::vector<double> t1(2 * 16 * 32);
-        for (unsigned k1 = 0; k1 < 16; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double a = -2.0 * kPi * double(k1 * n2) / 512.0;
-                t1[2 * (k1 * 32 + n2)] = std::cos(a);
-                t1[2 * (k1 * 32 + n2) + 1] = std::sin(a);
-            }
-        if ((st = upload<double>(pl, &pl->d_tw1, t1)) != SGX_OK) return st;
-        std::vector<double> wh(512), oh(512, 0.5);
-        for (unsigned i = 0; i < 512; ++i) wh[i] = 0.5 * double(pl->window[i]);
-        if ((st = upload<double>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_ones_half, oh)) != SGX_OK) return st;
-    }
+    if (const TunedKernel *k = tuned_kernel(pl->kind))
+        if ((st = tuned_tables<T>(pl, *k)) != SGX_OK) return st;
     if (pl->kind == K_BIGFFT) {  // global-memory transforms (bigfft.hip): stage twiddles, the two-level W_M table, chirp + transformed chirp
         BigHost h;
         if (!big_host_tables(n, h)) return set_err(pl, SGX_INTERNAL, "Internal error: K_BIGFFT plan at an unsupported length");
@@ -892,10 +872,7 @@ sgx_status build_device_tables(sgx_plan *pl) {
     if (pl->kind == K_BLUESTEIN && pl->bs_fwd_half) {  // half-length complex form: tables of length n / 2 (shared with the inverse rows)
         BsHostTables h;
         if (!bluestein_host_tables(n / 2, pl->dtype, h)) return set_err(pl, SGX_INTERNAL, "Internal error: chirp-z plan without a pass split");
-        if ((st = upload_cast<T>(pl, &pl->bs_half.chirp, h.chirp)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->bs_half.bhp, h.bhp)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->bs_half.tw, h.tw)) != SGX_OK) return st;
-        pl->bs_half.M = h.M;
+        if ((st = upload_bs<T>(pl, pl->bs_half, h)) != SGX_OK) return st;
     } else if (pl->kind == K_BLUESTEIN) {  // chirp-z tables (bluestein.hip), evaluated in f64
         const unsigned M = pl->bs_M;
         // c_j = e^(+i pi j^2 / n): the angle is reduced in integers, j^2 mod 2 n, so that a large j loses nothing
@@ -1010,25 +987,19 @@ void fill_args(const sgx_plan *pl, StftArgs &a, const void *x, void *out, size_t
 
 bool set_geometry(const sgx_plan *pl, StftArgs &a, KernelKind kind) {
     bool ok = false;
-    switch (kind) {
-    case K_R32X16_F32: ok = plan_geometry_r32x16_f32(a); break;
-    case K_R32X32_F32: ok = plan_geometry_r32x32_f32(a); break;
-    case K_D32X16_F64: ok = plan_geometry_d32x16_f64(a); break;
-    case K_D512_F64: ok = plan_geometry_d512_f64(a); break;
-    case K_R64X32_F32: ok = plan_geometry_r64x32_f32(a); break;
-    case K_D32X32_F64: ok = plan_geometry_d32x32_f64(a); break;
+    if (const TunedKernel *t = tuned_kernel(kind)) ok = t->geometry(a);
+    else switch (kind) {
     case K_LDS_RADIX2: ok = plan_geometry_lds_radix2(a, pl->dtype); break;
     case K_DIRECT_DFT: ok = plan_geometry_direct_dft(a, pl->dtype); break;
     case K_TWO_FACTOR: ok = plan_geometry_two_factor(a, pl->dtype); break;
     case K_REG_RADIX: ok = plan_geometry_reg_radix(a, pl->dtype); break;
     case K_BLUESTEIN: a.ft = 1; ok = pl->bs_M != 0 && (a.out_mode != OUT_MEL || a.mel_ptr != nullptr); break;
     case K_BIGFFT: a.ft = 2; ok = pl->big_n != 0 && a.out_mode != OUT_MEL; break;  // two frames per complex sequence; filterbanks: split path
+    default: break;  // (K_CQT has no frame tiles: run_cqt)
     }
     if (ok) a.tiles = (a.n_frames + a.ft - 1) / a.ft;
     return ok;
 }
-
-sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need);
 
 hipError_t launch_bluestein_plan(sgx_plan *pl, const StftArgs &a, hipStream_t s) {
     BsArgs b{};
@@ -1049,6 +1020,7 @@ hipError_t launch_bluestein_plan(sgx_plan *pl, const StftArgs &a, hipStream_t s)
 }
 
 hipError_t launch(sgx_plan *pl, const StftArgs &a, KernelKind kind, hipStream_t s) {
+    if (const TunedKernel *t = tuned_kernel(kind)) return t->launch(a, s);
     switch (kind) {
     case K_BIGFFT: {  // sequence scratch: sized by sgx_reserve, else grown here
         const size_t need = big_scratch_bytes(pl->big, pl->dtype, size_t(a.batch) * ((a.n_frames + 1u) / 2u));
@@ -1056,22 +1028,12 @@ hipError_t launch(sgx_plan *pl, const StftArgs &a, KernelKind kind, hipStream_t 
         return launch_big_stft(pl->big, a, pl->d_big, pl->dtype, s);
     }
     case K_BLUESTEIN: return launch_bluestein_plan(pl, a, s);
-    case K_R32X16_F32: return launch_r32x16_f32(a, s);
-    case K_R32X32_F32: return launch_r32x32_f32(a, s);
-    case K_D32X16_F64: return launch_d32x16_f64(a, s);
-    case K_D512_F64: return launch_d512_f64(a, s);
-    case K_R64X32_F32: return launch_r64x32_f32(a, s);
-    case K_D32X32_F64: return launch_d32x32_f64(a, s);
     case K_LDS_RADIX2: return launch_lds_radix2(a, pl->dtype, s);
     case K_TWO_FACTOR: return launch_two_factor(a, pl->dtype, s);
     case K_REG_RADIX: return launch_reg_radix(a, pl->dtype, s);
     default: return launch_direct_dft(a, pl->dtype, s);
     }
 }
-
-// The tuned kernel reads the samples through bounds-checked buffer loads, which only need the element's own alignment: any
-// base address and any row stride run on it (round 1 fell back to the register-tiled kernel for odd strides).
-KernelKind pick_kernel(const sgx_plan *pl, const void *, size_t) { return pl->kind; }
 
 sgx_status check_call(sgx_plan *pl, const void *samples, size_t batch, size_t n_samples, size_t stride,
                       void *out, size_t out_elems, size_t *n_frames_out) {
@@ -1091,8 +1053,6 @@ sgx_status check_call(sgx_plan *pl, const void *samples, size_t batch, size_t n_
     *n_frames_out = nf;
     return SGX_OK;
 }
-
-sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need);
 
 #ifndef SGX_SPLIT_BANK_BYTES
 // n_fft * sizeof(T) from which the filterbank runs as a second launch (f64 from n_fft 1600, f32 from 4096): measured per 64 x 10 s,
@@ -1118,6 +1078,24 @@ bool resolve_geometry(const sgx_plan *pl, StftArgs &a, KernelKind &kind) {
 }
 int chain_pos(KernelKind k) { return kind_is_tuned(k) ? 0 : k == K_REG_RADIX ? 1 : k == K_DIRECT_DFT ? 3 : 2; }  // (K_BLUESTEIN is chosen after the chain, at creation)
 
+// `iters` rounds of `launches` on stream s; with `ms`, the plan's events around them give the time per round
+template <typename F>
+sgx_status run_timed(sgx_plan *pl, hipStream_t s, int iters, float *ms, F launches) {
+    if (ms) SGX_HIP(pl, hipEventRecord(pl->ev0, s));
+    for (int i = 0; i < iters; ++i) {
+        const sgx_status st = launches();
+        if (st != SGX_OK) return st;
+    }
+    if (ms) {
+        SGX_HIP(pl, hipEventRecord(pl->ev1, s));
+        SGX_HIP(pl, hipEventSynchronize(pl->ev1));
+        float t = 0.f;
+        SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
+        *ms = t / float(iters);
+    }
+    return SGX_OK;
+}
+
 sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out, size_t n_frames,
                    hipStream_t s, int iters, float *ms) {
     CqtArgs a{};
@@ -1138,16 +1116,10 @@ sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, 
     a.len = static_cast<const unsigned *>(pl->d_cqt_len);
     a.amp = pl->amp;
     a.eps = pl->eps;
-    if (ms) SGX_HIP(pl, hipEventRecord(pl->ev0, s));
-    for (int i = 0; i < iters; ++i) SGX_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
-    if (ms) {
-        SGX_HIP(pl, hipEventRecord(pl->ev1, s));
-        SGX_HIP(pl, hipEventSynchronize(pl->ev1));
-        float t = 0.f;
-        SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
-        *ms = t / float(iters);
-    }
-    return SGX_OK;
+    return run_timed(pl, s, iters, ms, [&]() -> sgx_status {
+        SGX_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
+        return SGX_OK;
+    });
 }
 
 sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out,
@@ -1157,7 +1129,7 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
     void *stage_out = out;
     bool mfcc = pl->p.n_mfcc > 0;
     t_bank_stage = t_bank_epilogue = "";
-    KernelKind kind = pick_kernel(pl, x, stride);
+    KernelKind kind = pl->kind;  // (the tuned kernels read the samples through bounds-checked buffer loads, which only need the element's own alignment: any base address and any row stride run on them)
     // MFCC: fused into the tuned kernel's launch where the plan carries the basis fragments AND this call stays on that kernel (a call may
     // step down the chain, e.g. signals of fewer frames than half a tile); else the Mel-dB tensor goes to plan-owned scratch
     // (sgx_reserve sizes it ahead) and the DCT / lifter epilogue launch writes the caller's buffer
@@ -1197,8 +1169,7 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
     if (!resolve_geometry(pl, a1, kind))
         return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
     if (kind_is_tuned(kind)) a1.window = pl->d_window_half;
-    if (ms) SGX_HIP(pl, hipEventRecord(pl->ev0, s));
-    for (int i = 0; i < iters; ++i) {
+    const sgx_status st = run_timed(pl, s, iters, ms, [&]() -> sgx_status {
         SGX_HIP(pl, launch(pl, a1, kind, s));
         if (split_bank) SGX_HIP(pl, launch_bank_rows(pl->d_pwbuf, stage_out, a, pl->dtype, s));
         if (pl->p.freq_scale == SGX_FREQ_CHROMA)
@@ -1206,32 +1177,17 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
         if (mfcc)
             SGX_HIP(pl, launch_mfcc(pl->d_melbuf, out, pl->d_dct, pl->d_lifter, unsigned(batch), pl->p.n_mels, unsigned(n_frames),
                                     pl->p.n_mfcc, skip, pl->p.mfcc_lifter > 0, pl->dtype, s));
-    }
-    if (ms) {
-        SGX_HIP(pl, hipEventRecord(pl->ev1, s));
-        SGX_HIP(pl, hipEventSynchronize(pl->ev1));
-        float t = 0.f;
-        SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
-        *ms = t / float(iters);
-    }
+        return SGX_OK;
+    });
+    if (st != SGX_OK) return st;
     pl->bank_stage = t_bank_stage;  // (string literals: the name is put together when it is asked for)
     pl->bank_epilogue = t_bank_epilogue;
     return SGX_OK;
 }
 
-sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) SGX_HIP(pl, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    SGX_HIP(pl, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
-
 void free_device(sgx_plan *pl) {
     void **bufs[] = {&pl->d_window, &pl->d_tw, &pl->d_tw1, &pl->d_tw2, &pl->d_mel_ptr, &pl->d_mel_col,
-                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_melbuf, &pl->d_pwbuf, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_itwr2, &pl->d_itw12, &pl->d_itwrd, &pl->d_itw1d, &pl->d_frames, &pl->d_flag, &pl->d_ones, &pl->d_in, &pl->d_out, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->bs_half.chirp, &pl->bs_half.bhp, &pl->bs_half.tw, &pl->d_cqt_tab, &pl->d_cqt_info, &pl->d_cqt_len};
+                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_melbuf, &pl->d_pwbuf, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_frames, &pl->d_flag, &pl->d_ones, &pl->d_in, &pl->d_out, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->bs_half.chirp, &pl->bs_half.bhp, &pl->bs_half.tw, &pl->d_cqt_tab, &pl->d_cqt_info, &pl->d_cqt_len};
     for (void **b : bufs)
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     big_free(pl->big);
@@ -1253,6 +1209,74 @@ size_t istft_length(const sgx_params &p, size_t n_frames) {  // spectrogram.rs:4
     return (p.centre && unpadded > 0) ? unpadded : out_len;
 }
 
+// The fused tuned kernel carries the overlap from tile to tile (k_istft1024c: no halo frames), which needs ov = floor(1023 / hop) < 16
+// hop blocks of carry: hop >= 64.  (Rounds 1-3 recomputed the halo frames and left hops below 94 to the register-tiled rows +
+// overlap-add through a frame scratch; with the carry, 256 x 10 s: hop 90 1.77 -> 0.86 ms, hop 80 2.03 -> 0.91, hop 64 2.44 -> 1.08.)
+#ifndef SGX_ISTFT1024_MIN_HOP
+#define SGX_ISTFT1024_MIN_HOP 64
+#endif
+struct InverseCall {  // one sgx_istft: spectra [batch][n_fft / 2 + 1][n_frames] -> out [batch][out_len], the padded signal from `start`
+    const void *spec;
+    void *out;
+    unsigned n_frames, batch;
+    unsigned long long start, out_len;
+    hipStream_t s;
+};
+// The fused inverse kernels of single shapes, one entry each: the route name (sgx_istft_kernel_name), the plans it takes (dtype, n_fft,
+// hop >= min_hop: the overlap carried or recomputed on chip spans fewer than 16 hop blocks, ov = (n_fft - 1) / hop < 16; k_istft_d512
+// inverts two frames per transform), its tables and its launcher.  Tables: d_itw1 = the [tw1_rows][tw1_cols] grid W_N^(k1 n2),
+// N = n_fft / 2, between the two passes; with `twr`, d_itwr = conj(W_n_fft^k), k < n_fft / 2, of the real split.
+struct FusedInverse {
+    const char *route;
+    int dtype;
+    unsigned n_fft, min_hop, tw1_rows, tw1_cols;
+    bool twr;
+    hipError_t (*launch)(const sgx_plan *pl, const InverseCall &c);
+};
+double inverse_scale(const sgx_plan *pl) {  // T::one() / T::from_usize(n_fft) (fft_backend.rs:559-563), carried as a double
+    return pl->dtype == SGX_F64 ? 1.0 / double(pl->p.n_fft) : double(1.0f / float(pl->p.n_fft));
+}
+const FusedInverse kFusedInverse[] = {
+    {"istft1024c", SGX_F32, 1024, SGX_ISTFT1024_MIN_HOP, 32, 16, true, [](const sgx_plan *pl, const InverseCall &c) {
+         return launch_istft1024(c.spec, c.out, pl->d_window, c.n_frames, pl->p.hop_size, c.batch, c.start, c.out_len, float(inverse_scale(pl)),
+                                 (unsigned *)pl->d_flag, pl->d_itwr, pl->d_itw1, c.s);
+     }},
+    {"istft2048", SGX_F32, 2048, 128, 32, 32, true, [](const sgx_plan *pl, const InverseCall &c) {  // kernels_istft2048.hip
+         return launch_istft2048(c.spec, c.out, pl->d_window, c.n_frames, pl->p.hop_size, c.batch, c.start, c.out_len, float(inverse_scale(pl)),
+                                 (unsigned *)pl->d_flag, pl->d_itwr, pl->d_itw1, c.s);
+     }},
+    {"istft_d512", SGX_F64, 512, 32, 16, 32, false, [](const sgx_plan *pl, const InverseCall &c) {  // kernels_istft_d1024.hip: k_istft_d512
+         return launch_istft_d512(c.spec, c.out, pl->d_window, c.n_frames, pl->p.hop_size, c.batch, c.start, c.out_len, inverse_scale(pl),
+                                  (unsigned *)pl->d_flag, pl->d_itw1, c.s);
+     }},
+    {"istft_d1024", SGX_F64, 1024, 64, 16, 32, true, [](const sgx_plan *pl, const InverseCall &c) {  // kernels_istft_d1024.hip
+         return launch_istft_d1024(c.spec, c.out, pl->d_window, c.n_frames, pl->p.hop_size, c.batch, c.start, c.out_len, inverse_scale(pl),
+                                   (unsigned *)pl->d_flag, pl->d_itwr, pl->d_itw1, c.s);
+     }},
+};
+const FusedInverse *fused_inverse_of(const sgx_plan *pl) {  // the entry a plan of this shape carries tables for
+    for (const FusedInverse &f : kFusedInverse)
+        if (f.dtype == pl->dtype && f.n_fft == pl->p.n_fft && pl->p.hop_size >= f.min_hop) return &f;
+    return nullptr;
+}
+
+// Which fused inverse runs `n_frames` frames of `batch` spectra of this plan.  `tuned`: an entry of kFusedInverse — no frame scratch in
+// HBM; these kernels address one signal's spectrum with 32-bit byte offsets.  Else `reg`: the fused register-tiled kernel (every
+// length with a pass split, hop <= n_fft, at most half a tile of halo frames: the windowed frames never leave the chip).  Its launcher
+// has the last word (buffer alignment): run_istft launches it and takes the rows below when it declines; asked `ahead` of a call
+// (sgx_reserve), `reg` is the launcher's own geometry test.  Neither: rows into the frame scratch + overlap-add.
+struct InverseRoute {
+    const FusedInverse *tuned = nullptr;
+    bool reg = false;
+};
+InverseRoute inverse_route(const sgx_plan *pl, size_t batch, size_t n_frames, bool ahead) {
+    InverseRoute r;
+    if (pl->d_itw1 && n_frames * size_t(pl->nb_fft) * 2 * pl->elem < 0x7fffffffull) r.tuned = fused_inverse_of(pl);
+    if (!r.tuned && pl->kind != K_BIGFFT && n_frames <= 0xffffffffull && batch <= 0xffffffffull)
+        r.reg = !ahead || istft_reg_fuses(pl->d_window, pl->p.n_fft, unsigned(n_frames), pl->p.hop_size, unsigned(batch), pl->dtype);
+    return r;
+}
+
 template <typename T>
 sgx_status inverse_tables(sgx_plan *pl) {
     if (pl->d_itw || pl->d_flag) return SGX_OK;
@@ -1261,13 +1285,7 @@ sgx_status inverse_tables(sgx_plan *pl) {
         SGX_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
         return SGX_OK;
     }
-    std::vector<T> tw(2 * n);
-    for (size_t k = 0; k < n; ++k) {
-        const double a = -2.0 * kPi * double(k) / double(n);
-        tw[2 * k] = T(std::cos(a));
-        tw[2 * k + 1] = T(std::sin(a));
-    }
-    sgx_status st = upload<T>(pl, &pl->d_itw, tw);
+    sgx_status st = upload<T>(pl, &pl->d_itw, twiddle_vector<T>(unsigned(n), -2.0, unsigned(n)));
     if (st != SGX_OK) return st;
     // Even lengths whose rows have neither a register-tiled split (n / 2) nor a chirp-z convolution of their own in LDS (f64 above
     // 4096, f32 above 8192) invert through the chirp-z kernel in half-length complex form: tables of length n / 2.  (Before: the
@@ -1283,74 +1301,12 @@ sgx_status inverse_tables(sgx_plan *pl) {
         const bool own_fits = Mfull <= 16384ull && bluestein_fused_split(unsigned(Mfull), pl->dtype, &fa, &fb, &fc);
         if (!pl->bs_half.M && !own_fits && n >= 32 && n <= 32768 && n % 2 == 0 && (n & (n - 1)) != 0 && !pl->d_bs_bhp &&
             !reg_split_len(unsigned(n / 2), pl->dtype, &fa, &fb, &fc) && bluestein_host_tables(unsigned(n / 2), pl->dtype, h)) {
-            if ((st = upload_cast<T>(pl, &pl->bs_half.chirp, h.chirp)) != SGX_OK) return st;
-            if ((st = upload_cast<T>(pl, &pl->bs_half.bhp, h.bhp)) != SGX_OK) return st;
-            if ((st = upload_cast<T>(pl, &pl->bs_half.tw, h.tw)) != SGX_OK) return st;
-            pl->bs_half.M = h.M;
+            if ((st = upload_bs<T>(pl, pl->bs_half, h)) != SGX_OK) return st;
         }
     }
-    // The fused tuned kernel carries the overlap from tile to tile (k_istft1024c: no halo frames), which needs ov = floor(1023 / hop) < 16
-    // hop blocks of carry: hop >= 64.  (Rounds 1-3 recomputed the halo frames and left hops below 94 to the register-tiled rows +
-    // overlap-add through a frame scratch; with the carry, 256 x 10 s: hop 90 1.77 -> 0.86 ms, hop 80 2.03 -> 0.91, hop 64 2.44 -> 1.08.)
-#ifndef SGX_ISTFT1024_MIN_HOP
-#define SGX_ISTFT1024_MIN_HOP 64
-#endif
-    if (std::is_same<T, float>::value && n == 1024 && pl->p.hop_size >= SGX_ISTFT1024_MIN_HOP) {  // tables of the fused tuned kernel
-        std::vector<float> tr(2 * 32 * 16), t1(2 * 32 * 16);
-        for (unsigned n1 = 0; n1 < 32; ++n1)
-            for (unsigned n2 = 0; n2 < 16; ++n2) {
-                const double a = 2.0 * kPi * double(16 * n1 + n2) / 1024.0;  // conj(W_1024^k)
-                tr[2 * (n1 * 16 + n2)] = float(std::cos(a));
-                tr[2 * (n1 * 16 + n2) + 1] = float(std::sin(a));
-                const double b2 = -2.0 * kPi * double(n1 * n2) / 512.0;     // W_512^(k1 n2)
-                t1[2 * (n1 * 16 + n2)] = float(std::cos(b2));
-                t1[2 * (n1 * 16 + n2) + 1] = float(std::sin(b2));
-            }
-        if ((st = upload<float>(pl, &pl->d_itwr, tr)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_itw1, t1)) != SGX_OK) return st;
-    }
-    if (std::is_same<T, float>::value && n == 2048 && pl->p.hop_size >= 128) {  // tables of the fused tuned n_fft 2048 kernel (ov = 2047 / hop < 16)
-        std::vector<float> tr(2 * 1024), t1(2 * 32 * 32);
-        for (unsigned k = 0; k < 1024; ++k) {
-            const double a = 2.0 * kPi * double(k) / 2048.0;  // conj(W_2048^k)
-            tr[2 * k] = float(std::cos(a));
-            tr[2 * k + 1] = float(std::sin(a));
-        }
-        for (unsigned k1 = 0; k1 < 32; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double b2 = -2.0 * kPi * double(k1 * n2) / 1024.0;  // W_1024^(k1 n2)
-                t1[2 * (k1 * 32 + n2)] = float(std::cos(b2));
-                t1[2 * (k1 * 32 + n2) + 1] = float(std::sin(b2));
-            }
-        if ((st = upload<float>(pl, &pl->d_itwr2, tr)) != SGX_OK) return st;
-        if ((st = upload<float>(pl, &pl->d_itw12, t1)) != SGX_OK) return st;
-    }
-    if (std::is_same<T, double>::value && n == 512 && pl->p.hop_size >= 32) {  // table of the fused f64 n_fft 512 kernel (two frames per transform): W_512^(k1 n2)
-        std::vector<double> t1(2 * 16 * 32);
-        for (unsigned k1 = 0; k1 < 16; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double b2 = -2.0 * kPi * double(k1 * n2) / 512.0;
-                t1[2 * (k1 * 32 + n2)] = std::cos(b2);
-                t1[2 * (k1 * 32 + n2) + 1] = std::sin(b2);
-            }
-        if ((st = upload<double>(pl, &pl->d_itw1d, t1)) != SGX_OK) return st;
-        pl->istft_d512 = true;
-    }
-    if (std::is_same<T, double>::value && n == 1024 && pl->p.hop_size >= 64) {  // tables of the fused tuned f64 n_fft 1024 kernel (ov = 1023 / hop < 16)
-        std::vector<double> tr(2 * 512), t1(2 * 16 * 32);
-        for (unsigned k = 0; k < 512; ++k) {
-            const double a = 2.0 * kPi * double(k) / 1024.0;  // conj(W_1024^k)
-            tr[2 * k] = std::cos(a);
-            tr[2 * k + 1] = std::sin(a);
-        }
-        for (unsigned k1 = 0; k1 < 16; ++k1)
-            for (unsigned n2 = 0; n2 < 32; ++n2) {
-                const double b2 = -2.0 * kPi * double(k1 * n2) / 512.0;  // W_512^(k1 n2)
-                t1[2 * (k1 * 32 + n2)] = std::cos(b2);
-                t1[2 * (k1 * 32 + n2) + 1] = std::sin(b2);
-            }
-        if ((st = upload<double>(pl, &pl->d_itwrd, tr)) != SGX_OK) return st;
-        if ((st = upload<double>(pl, &pl->d_itw1d, t1)) != SGX_OK) return st;
+    if (const FusedInverse *f = fused_inverse_of(pl)) {
+        if (f->twr && (st = upload<T>(pl, &pl->d_itwr, twiddle_vector<T>(unsigned(n / 2), 2.0, unsigned(n)))) != SGX_OK) return st;
+        if ((st = upload<T>(pl, &pl->d_itw1, twiddle_grid<T>(f->tw1_rows, f->tw1_cols))) != SGX_OK) return st;
     }
     SGX_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
     return SGX_OK;
@@ -1371,7 +1327,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
     if (frame_fast) { c.in_ks = n_frames; c.in_rs = 1; c.k_fast = 0; }  // [bin][frame] (StftResult layout, S9)
     else { c.in_ks = 1; c.in_rs = pl->nb_fft; c.k_fast = 1; }
     if (pl->kind == K_BIGFFT) {  // rows through global memory (two frames per complex sequence, the forward engine behind conj)
-        c.scale = pl->dtype == SGX_F64 ? 1.0 / double(n) : double(1.0f / float(n));
+        c.scale = inverse_scale(pl);
         c.win = win;
         c.bad_flag = (unsigned *)pl->d_flag;
         sgx_status st = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, batch * ((n_frames + 1) / 2)));
@@ -1384,7 +1340,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
     if (c.tile == 0) return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
     c.tiles = unsigned((n_frames + c.tile - 1) / c.tile);
     c.tw = pl->d_itw;
-    c.scale = pl->dtype == SGX_F64 ? 1.0 / double(n) : double(1.0f / float(n));  // T::one() / T::from_usize(n_fft)
+    c.scale = inverse_scale(pl);
     c.win = win;
     c.bad_flag = (unsigned *)pl->d_flag;
     // register-tiled passes; at lengths without a split the chirp-z rows (a plan of such a length carries the tables); else the
@@ -1420,43 +1376,18 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
     sgx_status st;
     const size_t n = pl->p.n_fft;
     SGX_HIP(pl, hipMemsetAsync(pl->d_flag, 0, sizeof(unsigned), s));
-    // fused tuned kernel: no frame scratch in HBM; it addresses one signal's spectrum with 32-bit byte offsets
-    if (pl->d_itwr && n_frames * 513ull * 8ull < 0x7fffffffull) {
-        const size_t pad0 = pl->p.centre ? n / 2 : 0;
-        const size_t full0 = (n_frames - 1) * size_t(pl->p.hop_size) + n;
-        SGX_HIP(pl, launch_istft1024(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch),
-                                     out_len == full0 ? 0 : pad0, out_len, 1.0f / 1024.0f, (unsigned *)pl->d_flag, pl->d_itwr,
-                                     pl->d_itw1, s));
-        *route = "istft1024c";
-        return SGX_OK;
-    }
     const size_t pad = pl->p.centre ? n / 2 : 0;
     const size_t full = (n_frames - 1) * size_t(pl->p.hop_size) + n;
     const size_t start = out_len == full ? 0 : pad;  // untrimmed when the centred signal would be empty (:4933)
-    if (pl->d_itwr2 && n_frames * 1025ull * 8ull < 0x7fffffffull) {  // fused tuned kernel at n_fft 2048 (kernels_istft2048.hip)
-        SGX_HIP(pl, launch_istft2048(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0f / 2048.0f,
-                                     (unsigned *)pl->d_flag, pl->d_itwr2, pl->d_itw12, s));
-        *route = "istft2048";
+    const InverseRoute r = inverse_route(pl, batch, n_frames, false);
+    if (r.tuned) {
+        SGX_HIP(pl, r.tuned->launch(pl, InverseCall{spec, out, unsigned(n_frames), unsigned(batch), start, out_len, s}));
+        *route = r.tuned->route;
         return SGX_OK;
     }
-    if (pl->istft_d512 && n_frames * 257ull * 16ull < 0x7fffffffull) {  // fused f64 kernel at n_fft 512 (kernels_istft_d1024.hip: k_istft_d512)
-        SGX_HIP(pl, launch_istft_d512(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0 / 512.0,
-                                      (unsigned *)pl->d_flag, pl->d_itw1d, s));
-        *route = "istft_d512";
-        return SGX_OK;
-    }
-    if (pl->d_itwrd && n_frames * 513ull * 16ull < 0x7fffffffull) {  // fused tuned f64 kernel at n_fft 1024 (kernels_istft_d1024.hip)
-        SGX_HIP(pl, launch_istft_d1024(spec, out, pl->d_window, unsigned(n_frames), pl->p.hop_size, unsigned(batch), start, out_len, 1.0 / 1024.0,
-                                       (unsigned *)pl->d_flag, pl->d_itwrd, pl->d_itw1d, s));
-        *route = "istft_d1024";
-        return SGX_OK;
-    }
-    // fused register-tiled kernel (every length with a pass split, hop <= n_fft, at most half a tile of halo frames): the windowed
-    // frames never leave the chip
-    if (pl->kind != K_BIGFFT && n_frames <= 0xffffffffull && batch <= 0xffffffffull) {
+    if (r.reg) {
         const hipError_t e = launch_istft_reg(spec, out, pl->d_window, pl->d_itw, unsigned(n), unsigned(n_frames), pl->p.hop_size, unsigned(batch),
-                                              start, out_len, pl->dtype == SGX_F64 ? 1.0 / double(n) : double(1.0f / float(n)),
-                                              (unsigned *)pl->d_flag, pl->dtype, s);
+                                              start, out_len, inverse_scale(pl), (unsigned *)pl->d_flag, pl->dtype, s);
         if (e == hipSuccess) {
             *route = "istft_reg";
             return SGX_OK;
@@ -1481,6 +1412,62 @@ sgx_status check_flag(sgx_plan *pl, hipStream_t s) {
     SGX_HIP(pl, hipStreamSynchronize(s));
     if (flag)  // realfft: FftError::InputValues, mapped at fft_backend.rs:555-557
         return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: imaginary part of the DC or Nyquist bin is non-zero");
+    return SGX_OK;
+}
+
+// What every plan starts from: the caller's parameters with the custom window detached, the scalar type, the STFT window, and the
+// amplitude stage by S6 — dB is applied only when LogParams were supplied; Decibels without them returns power
+sgx_plan *new_plan(const sgx_params &params) {
+    sgx_plan *pl = new (std::nothrow) sgx_plan();
+    if (!pl) return nullptr;
+    pl->p = params;
+    if (params.window_kind == SGX_WIN_CUSTOM) pl->custom_window.assign(params.custom_window, params.custom_window + params.n_fft);
+    pl->p.custom_window = nullptr;
+    pl->dtype = params.dtype;
+    pl->elem = params.dtype == SGX_F64 ? 8 : 4;
+    pl->nb_fft = params.n_fft / 2 + 1;
+    pl->amp = params.amp_scale == SGX_AMP_MAGNITUDE ? AMP_MAGNITUDE
+              : (params.amp_scale == SGX_AMP_DECIBELS && params.has_log_params) ? AMP_DB : AMP_POWER;
+    pl->eps = pl->amp == AMP_DB ? std::pow(10.0, params.floor_db / 10.0) : 0.0;
+    build_window(pl->p, pl->custom_window, pl->window);
+    return pl;
+}
+
+// The last step of plan creation: resolve the device (sgx_params.device; -1: the current one, -2: host-only plan, nothing to open),
+// create the plan's events and build its device tables with `init` on that device.  Hands the plan to the caller, or destroys it.
+sgx_status open_plan(sgx_plan *pl, sgx_plan **out, sgx_status (*init)(sgx_plan *)) {
+    pl->device = pl->p.device;
+    if (pl->p.device != -2) {
+        int ndev = 0;
+        hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev <= 0) {
+            delete pl;
+            return create_fail(SGX_BACKEND, std::string("hip -- FFT backend error: no HIP device available (") + hipGetErrorString(e) + ")");
+        }
+        int dev = pl->p.device;
+        if (dev == -1 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+        if (dev < 0 || dev >= ndev) {
+            delete pl;
+            return create_fail(SGX_INVALID_INPUT, "Invalid input: device ordinal out of range");
+        }
+        pl->device = dev;
+        DeviceGuard dg;
+        auto dev_init = [&]() -> sgx_status {
+            SGX_HIP(pl, dg.enter(dev));
+            SGX_HIP(pl, hipEventCreate(&pl->ev0));
+            SGX_HIP(pl, hipEventCreate(&pl->ev1));
+            return init(pl);
+        };
+        const sgx_status st = dev_init();
+        if (st != SGX_OK) {
+            g_create_err = pl->err;
+            free_device(pl);
+            delete pl;
+            return st;
+        }
+        pl->device_ready = true;
+    }
+    *out = pl;
     return SGX_OK;
 }
 
@@ -1509,13 +1496,8 @@ const char *sgx_bank_stage_name(const sgx_plan *plan) {
 
 const char *sgx_kernel_name(const sgx_plan *plan) {
     if (!plan) return "";
+    if (const TunedKernel *t = tuned_kernel(plan->kind)) return t->name;
     switch (plan->kind) {
-    case K_R32X16_F32: return "r32x16_f32";
-    case K_R32X32_F32: return "r32x32_f32";
-    case K_D32X16_F64: return "d32x16_f64";
-    case K_D512_F64: return "d512_f64";
-    case K_R64X32_F32: return "r64x32_f32";
-    case K_D32X32_F64: return "d32x32_f64";
     case K_LDS_RADIX2: return "lds_radix2";
     case K_TWO_FACTOR: return "two_factor_dft";
     case K_REG_RADIX: return "reg_radix";
@@ -1537,17 +1519,9 @@ sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
     // Frames past the global-memory transforms' range (bigfft.hip: 2^20, powers of two 2^21) fail here, before gigabytes of host tables
     // are built for them (n_fft = 2^30 + 2: 49 s and 8.7 GB to reach the same answer further down)
     if (params->n_fft > (1u << 15) && !big_supported(params->n_fft))
-        return create_fail(SGX_BACKEND, "hip -- FFT backend error: n_fft too large (the global-memory transforms take n_fft up to 2^20, powers of two up to 2^21)");
-    sgx_plan *pl = new (std::nothrow) sgx_plan();
+        return create_fail(SGX_BACKEND, kNfftTooLarge);
+    sgx_plan *pl = new_plan(*params);
     if (!pl) return create_fail(SGX_INTERNAL, "Internal error: out of memory");
-    pl->p = *params;
-    if (params->window_kind == SGX_WIN_CUSTOM) {
-        pl->custom_window.assign(params->custom_window, params->custom_window + params->n_fft);
-    }
-    pl->p.custom_window = nullptr;
-    pl->dtype = params->dtype;
-    pl->elem = params->dtype == SGX_F64 ? 8 : 4;
-    pl->nb_fft = params->n_fft / 2 + 1;
     if (params->freq_scale == SGX_FREQ_CHROMA) pl->p.n_mels = 12;  // N_CHROMA rows go through the mapping slot
     // Mel and LogHz are both sparse row mappings of the power spectrum (MappingKind::{Mel, LogHz}, :1845-1865): one path
     pl->out_mode = params->amp_scale == SGX_AMP_COMPLEX ? OUT_COMPLEX
@@ -1555,35 +1529,28 @@ sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
     pl->n_out = pl->out_mode == OUT_MEL ? pl->p.n_mels : pl->nb_fft;
     const unsigned mfcc_skip = (params->n_mfcc > 1 && !params->mfcc_include_c0) ? 1u : 0u;  // src/mfcc.rs:262-268
     pl->n_final = params->n_mfcc > 0 ? params->n_mfcc - mfcc_skip : pl->n_out;
-    // S6: dB is applied only when LogParams were supplied; Decibels without them returns power
-    pl->amp = params->amp_scale == SGX_AMP_MAGNITUDE ? AMP_MAGNITUDE
-              : (params->amp_scale == SGX_AMP_DECIBELS && params->has_log_params) ? AMP_DB : AMP_POWER;
-    if (params->freq_scale == SGX_FREQ_CHROMA) pl->amp = AMP_MAG_IN;  // the bank weighs magnitudes; nothing after it
-    pl->eps = pl->amp == AMP_DB ? std::pow(10.0, params->floor_db / 10.0) : 0.0;
-    build_window(pl->p, pl->custom_window, pl->window);
+    if (params->freq_scale == SGX_FREQ_CHROMA) pl->amp = AMP_MAG_IN;  // the bank weighs magnitudes (validate: amp_scale = magnitude); nothing after it
     if (params->freq_scale == SGX_FREQ_MEL) build_mel_csr(pl->p, pl->mel_ptr, pl->mel_col, pl->mel_val);
     if (params->freq_scale == SGX_FREQ_LOGHZ) build_loghz_csr(pl->p, pl->mel_ptr, pl->mel_col, pl->mel_val, pl->loghz_freqs);
     if (params->freq_scale == SGX_FREQ_CHROMA) build_chroma_csr(pl->p, pl->mel_ptr, pl->mel_col, pl->mel_val);
     if (params->freq_scale == SGX_FREQ_ERB) build_erb_dense(pl->p, pl->mel_ptr, pl->mel_col, pl->mel_val, pl->loghz_freqs);
+    if (pl->out_mode == OUT_MEL) {
+        bool contig = true;
+        for (size_t m = 0; m < pl->p.n_mels && contig; ++m)
+            for (uint32_t i = pl->mel_ptr[m]; i + 1 < pl->mel_ptr[m + 1]; ++i)
+                contig = contig && (pl->mel_col[i + 1] == pl->mel_col[i] + 1);
+        pl->mel_contig = contig ? 1u : 0u;
+    }
 
     const bool pow2 = params->n_fft >= 4 && (params->n_fft & (params->n_fft - 1)) == 0;
     // powers of two (32..8192) and the listed even composite sizes: register-tiled kernel; other powers of two: LDS radix-2;
     // other composite lengths: two-factor DFT; primes fall through to the direct sum
     pl->kind = (pow2 || params->n_fft % 2 == 0) ? K_REG_RADIX : K_TWO_FACTOR;  // (even sizes outside the register-tiled list fall through)
-    if (params->dtype == SGX_F32 && params->n_fft == 1024 && (SGX_ODDHOP || params->hop_size % 2 == 0)) pl->kind = K_R32X16_F32;
-    // n_fft 512 (two frames per transform): staged variants at hops 64 / 128 / 160 / 256, the packed form's per-lane loads at every other even hop (per-bin outputs)
-    if (params->dtype == SGX_F32 && params->n_fft == 512 && params->hop_size % 2 == 0 && params->hop_size <= 512) pl->kind = K_R32X16_F32;  // per-bin outputs (else falls back)
-    if (params->dtype == SGX_F32 && params->n_fft == 2048) pl->kind = K_R32X32_F32;  // (odd hops: register-tiled kernel)
-    if (params->dtype == SGX_F64 && params->n_fft == 1024) pl->kind = K_D32X16_F64;  // per-bin and complex outputs (filterbanks, odd hops: register-tiled kernel)
-    if (params->dtype == SGX_F64 && params->n_fft == 512 && params->hop_size <= 260) pl->kind = K_D512_F64;  // two frames per transform
-    if (params->dtype == SGX_F32 && params->n_fft == 4096) pl->kind = K_R64X32_F32;  // per-bin and complex outputs; filterbanks: split path
-    if (params->dtype == SGX_F64 && params->n_fft == 2048) pl->kind = K_D32X32_F64;  // per-bin and complex outputs
-    if (pl->kind == K_R32X16_F32) build_band_schedule(pl);  // before the kind is resolved: plan_geometry_r32x16_f32 asks for it
-    if (pl->kind == K_R32X32_F32) build_band_schedule(pl, 8, r32x32::kSegs2, r32x32::kSch2MaxWords, 0);
-    if (pl->kind == K_D32X16_F64) build_band_schedule(pl, 8, d32x16::kDSegs, d32x16::kDSchMaxWords, 0, 2);
-    if (pl->kind == K_D512_F64) build_band_schedule(pl, 8, d512::kSegs, d512::kSchMaxWords, 0, 2);
-    if (pl->kind == K_R64X32_F32) build_band_schedule(pl, 16, 2, 1u << 20, 0, 1);  // (as k_d32x32's, 4-byte weights)
-    if (pl->kind == K_D32X32_F64) build_band_schedule(pl, 16, 2, 1u << 20, 0, 2);  // 16 half-waves x 8 slots; the table stays in global memory (kernels_d32x32.hip)
+    for (const TunedKernel &t : kTuned)
+        if (t.dtype == params->dtype && t.selects(*params)) {
+            pl->kind = t.kind;
+            build_band_schedule(pl, t);  // before the kind is resolved: the kernel's plan_geometry asks for it
+        }
     {
         StftArgs probe;
         fill_args(pl, probe, nullptr, nullptr, 1, params->n_fft, params->n_fft, 1);
@@ -1666,57 +1633,26 @@ sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
         }
         if (!ok) {
             delete pl;
-            return create_fail(SGX_BACKEND, "hip -- FFT backend error: n_fft too large (the global-memory transforms take n_fft up to 2^20, powers of two up to 2^21)");
+            return create_fail(SGX_BACKEND, kNfftTooLarge);
         }
         pl->kind = kind;
     }
 
-    pl->device = params->device;
-    if (params->device != -2) {
-        int ndev = 0;
-        hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) {
-            delete pl;
-            return create_fail(SGX_BACKEND, std::string("hip -- FFT backend error: no HIP device available (") +
-                                                hipGetErrorString(e) + ")");
-        }
-        int dev = params->device;
-        if (dev == -1 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (dev < 0 || dev >= ndev) {
-            delete pl;
-            return create_fail(SGX_INVALID_INPUT, "Invalid input: device ordinal out of range");
-        }
-        pl->device = dev;
-        DeviceGuard dg;
-        auto dev_init = [&]() -> sgx_status {
-            SGX_HIP(pl, dg.enter(dev));
-            SGX_HIP(pl, hipEventCreate(&pl->ev0));
-            SGX_HIP(pl, hipEventCreate(&pl->ev1));
-            sgx_status s2 = pl->dtype == SGX_F64 ? build_device_tables<double>(pl) : build_device_tables<float>(pl);
-            if (s2 != SGX_OK) return s2;
-            // Everything the per-frame entry points (sgx_r2c / sgx_c2r = R2cPlan / C2rPlan::process) need is allocated here, so
-            // that `process` never allocates (src/fft_backend.rs:21-24): one frame of staging each way, the rectangular window,
-            // the inverse tables and the DC/Nyquist flag.  Batched calls size their scratch through sgx_reserve.
-            const size_t frame_bytes = 2 * size_t(pl->nb_fft) * pl->elem;
-            if (pl->kind == K_BIGFFT && (s2 = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return s2;  // one sequence: the per-frame entry points
-            if ((s2 = grow(pl, &pl->d_in, &pl->d_in_bytes, frame_bytes)) != SGX_OK) return s2;
-            if ((s2 = grow(pl, &pl->d_out, &pl->d_out_bytes, frame_bytes)) != SGX_OK) return s2;
-            std::vector<double> ones(pl->p.n_fft, 1.0);
-            s2 = pl->dtype == SGX_F64 ? upload_cast<double>(pl, &pl->d_ones, ones) : upload_cast<float>(pl, &pl->d_ones, ones);
-            if (s2 != SGX_OK) return s2;
-            return pl->dtype == SGX_F64 ? inverse_tables<double>(pl) : inverse_tables<float>(pl);
-        };
-        st = dev_init();
-        if (st != SGX_OK) {
-            g_create_err = pl->err;
-            free_device(pl);
-            delete pl;
-            return st;
-        }
-        pl->device_ready = true;
-    }
-    *out = pl;
-    return SGX_OK;
+    return open_plan(pl, out, [](sgx_plan *pl) -> sgx_status {
+        sgx_status s2 = pl->dtype == SGX_F64 ? build_device_tables<double>(pl) : build_device_tables<float>(pl);
+        if (s2 != SGX_OK) return s2;
+        // Everything the per-frame entry points (sgx_r2c / sgx_c2r = R2cPlan / C2rPlan::process) need is allocated here, so
+        // that `process` never allocates (src/fft_backend.rs:21-24): one frame of staging each way, the rectangular window,
+        // the inverse tables and the DC/Nyquist flag.  Batched calls size their scratch through sgx_reserve.
+        const size_t frame_bytes = 2 * size_t(pl->nb_fft) * pl->elem;
+        if (pl->kind == K_BIGFFT && (s2 = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return s2;  // one sequence: the per-frame entry points
+        if ((s2 = grow(pl, &pl->d_in, &pl->d_in_bytes, frame_bytes)) != SGX_OK) return s2;
+        if ((s2 = grow(pl, &pl->d_out, &pl->d_out_bytes, frame_bytes)) != SGX_OK) return s2;
+        std::vector<double> ones(pl->p.n_fft, 1.0);
+        s2 = pl->dtype == SGX_F64 ? upload_cast<double>(pl, &pl->d_ones, ones) : upload_cast<float>(pl, &pl->d_ones, ones);
+        if (s2 != SGX_OK) return s2;
+        return pl->dtype == SGX_F64 ? inverse_tables<double>(pl) : inverse_tables<float>(pl);
+    });
 }
 
 sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out) {
@@ -1729,60 +1665,18 @@ sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *c
     if (st != SGX_OK) return create_fail(st, msg);
     if ((st = cqt_validate(*params, *cqt, msg)) != SGX_OK) return create_fail(st, msg);
     if (params->n_fft > (1u << 15) && !big_supported(params->n_fft))  // (the same frame-length range as every other plan)
-        return create_fail(SGX_BACKEND, "hip -- FFT backend error: n_fft too large (the global-memory transforms take n_fft up to 2^20, powers of two up to 2^21)");
-    sgx_plan *pl = new (std::nothrow) sgx_plan();
+        return create_fail(SGX_BACKEND, kNfftTooLarge);
+    sgx_plan *pl = new_plan(*params);  // (its window: the STFT window of sgx_window; the CQT itself reads unwindowed frames)
     if (!pl) return create_fail(SGX_INTERNAL, "Internal error: out of memory");
-    pl->p = *params;
-    if (params->window_kind == SGX_WIN_CUSTOM) pl->custom_window.assign(params->custom_window, params->custom_window + params->n_fft);
-    pl->p.custom_window = nullptr;
-    pl->dtype = params->dtype;
-    pl->elem = params->dtype == SGX_F64 ? 8 : 4;
-    pl->nb_fft = params->n_fft / 2 + 1;
     pl->kind = K_CQT;
     pl->out_mode = OUT_MEL;  // a mapping of the frame to n_bins rows
-    build_window(pl->p, pl->custom_window, pl->window);  // the STFT window (sgx_window); the CQT itself reads unwindowed frames
     build_cqt_kernels(pl->p, *cqt, pl->cqt_len, pl->cqt_re, pl->cqt_im, pl->cqt_freqs);
     pl->n_out = pl->n_final = unsigned(pl->cqt_len.size());
     pl->p.n_mels = pl->n_out;
-    pl->amp = params->amp_scale == SGX_AMP_MAGNITUDE ? AMP_MAGNITUDE
-              : (params->amp_scale == SGX_AMP_DECIBELS && params->has_log_params) ? AMP_DB : AMP_POWER;  // S6
-    pl->eps = pl->amp == AMP_DB ? std::pow(10.0, params->floor_db / 10.0) : 0.0;
     pl->cqt_groups = (pl->n_out + 7) / 8;
     pl->cqt_lpad = (*std::max_element(pl->cqt_len.begin(), pl->cqt_len.end()) + 15u) & ~15u;
     pl->cqt_m = cqt_lds_m(params->hop_size, pl->cqt_lpad, pl->dtype);
-    pl->device = params->device;
-    if (params->device != -2) {
-        int ndev = 0;
-        hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) {
-            delete pl;
-            return create_fail(SGX_BACKEND, std::string("hip -- FFT backend error: no HIP device available (") + hipGetErrorString(e) + ")");
-        }
-        int dev = params->device;
-        if (dev == -1 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (dev < 0 || dev >= ndev) {
-            delete pl;
-            return create_fail(SGX_INVALID_INPUT, "Invalid input: device ordinal out of range");
-        }
-        pl->device = dev;
-        DeviceGuard dg;
-        auto dev_init = [&]() -> sgx_status {
-            SGX_HIP(pl, dg.enter(dev));
-            SGX_HIP(pl, hipEventCreate(&pl->ev0));
-            SGX_HIP(pl, hipEventCreate(&pl->ev1));
-            return pl->dtype == SGX_F64 ? cqt_device_tables<double>(pl) : cqt_device_tables<float>(pl);
-        };
-        st = dev_init();
-        if (st != SGX_OK) {
-            g_create_err = pl->err;
-            free_device(pl);
-            delete pl;
-            return st;
-        }
-        pl->device_ready = true;
-    }
-    *out = pl;
-    return SGX_OK;
+    return open_plan(pl, out, [](sgx_plan *pl) { return pl->dtype == SGX_F64 ? cqt_device_tables<double>(pl) : cqt_device_tables<float>(pl); });
 }
 
 sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im) {
@@ -2003,11 +1897,9 @@ sgx_status sgx_reserve(sgx_plan *plan, size_t batch, size_t n_samples, int32_t h
         (st = grow(plan, &plan->d_big, &plan->d_big_bytes, big_scratch_bytes(plan->big, plan->dtype, batch * ((nf + 1) / 2)))) != SGX_OK)
         return st;
     if (inverse) {  // sgx_istft of `batch` spectra whose frame count is that of n_samples-long signals
-        // the same tests run_istft applies: tuned n_fft = 1024 kernel, else the fused register-tiled kernel; only the unfused
-        // fallback (rows + overlap-add) touches the frame scratch
-        const bool fused = (plan->d_itwr && nf * 513ull * 8ull < 0x7fffffffull) || (plan->d_itwr2 && nf * 1025ull * 8ull < 0x7fffffffull) || (plan->d_itwrd && nf * 513ull * 16ull < 0x7fffffffull) || (plan->istft_d512 && nf * 257ull * 16ull < 0x7fffffffull) ||
-                           (plan->kind != K_BIGFFT && nf <= 0xffffffffull && batch <= 0xffffffffull &&
-                            istft_reg_fuses(plan->d_window, plan->p.n_fft, unsigned(nf), plan->p.hop_size, unsigned(batch), plan->dtype));
+        // only the unfused route (rows + overlap-add) touches the frame scratch
+        const InverseRoute r = inverse_route(plan, batch, nf, true);
+        const bool fused = r.tuned || r.reg;
         if (!fused && (st = grow(plan, &plan->d_frames, &plan->d_frames_bytes, batch * nf * plan->p.n_fft * plan->elem)) != SGX_OK) return st;
     }
     if (host_staging) {

@@ -20,7 +20,6 @@ enum OutMode : int { OUT_LINEAR = 0, OUT_MEL = 1, OUT_COMPLEX = 2, OUT_BINAURAL 
 // AMP_MAG_IN: the mapping consumes sqrt(power) and its output is final (chromagram: bank applied to magnitudes)
 enum AmpMode : int { AMP_POWER = 0, AMP_MAGNITUDE = 1, AMP_DB = 2, AMP_MAG_IN = 3 };
 enum KernelKind : int { K_DIRECT_DFT = 0, K_LDS_RADIX2 = 1, K_R32X16_F32 = 2, K_TWO_FACTOR = 3, K_REG_RADIX = 4, K_BLUESTEIN = 5, K_R32X32_F32 = 6, K_D32X16_F64 = 7, K_D512_F64 = 8, K_R64X32_F32 = 9, K_D32X32_F64 = 10, K_BIGFFT = 11, K_CQT = 12 };
-inline bool kind_is_tuned(KernelKind k) { return k == K_R32X16_F32 || k == K_R32X32_F32 || k == K_D32X16_F64 || k == K_D512_F64 || k == K_R64X32_F32 || k == K_D32X32_F64; }  // the shape-specific kernels at the head of the chain
 
 // Kernel arguments (POD, passed by value).  Layouts in HBM:
 //   x      : [batch][sample_stride] T, row b valid for n_samples elements
@@ -428,10 +427,7 @@ struct sgx_plan {
     void *d_window_half = nullptr, *d_ones_half = nullptr;  // 0.5*window (exact) for the tuned kernel's real split
     // inverse path (sgx_istft / sgx_c2r), created on first use: full twiddle table e^{-2 pi i k/n}, frame scratch, flag
     void *d_itw = nullptr, *d_frames = nullptr, *d_flag = nullptr;
-    void *d_itwr = nullptr, *d_itw1 = nullptr;  // tuned f32 n_fft = 1024 inverse: conj(W_1024^k) [32][16], W_512^(k1 n2) [32][16]
-    void *d_itwr2 = nullptr, *d_itw12 = nullptr;  // tuned f32 n_fft = 2048 inverse: conj(W_2048^k) [1024], W_1024^(k1 n2) [32][32]
-    bool istft_d512 = false;  // f64 n_fft 512, hop >= 32: the fused two-frames-per-transform inverse (d_itw1d holds its W_512^(k1 n2))
-    void *d_itwrd = nullptr, *d_itw1d = nullptr;  // tuned f64 n_fft = 1024 inverse: conj(W_1024^k) [512], W_512^(k1 n2) [16][32] (f64)
+    void *d_itwr = nullptr, *d_itw1 = nullptr;  // tables of the plan's fused inverse of a single shape, if it has one (plan.hip kFusedInverse)
     // K_BLUESTEIN: chirp, transformed chirp, length-M twiddles (the sequences themselves never leave LDS: no frame scratch)
     void *d_bs_chirp = nullptr, *d_bs_tw = nullptr, *d_bs_wc = nullptr, *d_bs_bhp = nullptr;
     unsigned bs_M = 0;

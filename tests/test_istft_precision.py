@@ -282,8 +282,11 @@ def frames_for(dtype, n_fft, hop):
 # ---- CPU: names, reference pin, calibration -----------------------------------------------------------------------------------
 def test_route_table_names_every_route_the_code_sets():
     src = open(os.path.join(os.path.dirname(__file__), "..", "spectrograms_amd", "csrc", "plan.hip")).read()
-    body = src[src.index("sgx_status launch_c2r_frames("):src.index("sgx_status check_flag(")]
-    code = set(re.findall(r'(?:\*route|\br) = "([^"]+)"', body)) | set(re.findall(r'\{"[^"]+", "([^"]+)"\}', body))
+    # the inverse path: the table of fused inverses of single shapes (entries {"name", SGX_F32 / SGX_F64, ...}), the rows' launchers, run_istft
+    body = src[src.index("const FusedInverse kFusedInverse[] = {"):src.index("sgx_status check_flag(")]
+    code = (set(re.findall(r'(?:\*route|\br) = "([^"]+)"', body)) | set(re.findall(r'\{"[^"]+", "([^"]+)"\}', body))
+            | set(re.findall(r'\{"([^"]+)", SGX_F(?:32|64),', body)))
+    assert "route = r.tuned->route" in body  # (the table's names are reported from there)
     assert code == NAMES, code ^ NAMES
     table = {c[5] for c in ROUTES} | {c[2] for c in SINGLE}
     assert table == NAMES, table ^ NAMES
