@@ -32,14 +32,15 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
  *    on one plan that go to different streams must be ordered by the caller (events), as must a host-pointer call behind a
  *    device-pointer call still in flight.  A call does not depend on the calls before it: a larger, smaller, failed, host- or
  *    device-pointer call in between changes neither the bits nor the route of the next one (the DC / Nyquist flag word is
- *    cleared per call).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
+ *    cleared per call; the one exception is the state a streaming FIR plan exists to carry: sgx_fir_process reads and replaces
+ *    the plan's history, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
  *    by tests/test_stream_order.py.
@@ -469,6 +470,63 @@ sgx_status sgx_gammatone_reserve(sgx_gammatone *plan, size_t batch, size_t n_sam
 const char *sgx_gammatone_kernel_name(const sgx_gammatone *plan); /* "k_gammatone_iir": one kernel for every shape and both types */
 int32_t sgx_gammatone_device(const sgx_gammatone *plan);
 const char *sgx_gammatone_last_error(const sgx_gammatone *plan); /* NULL plan: the text of the last failed create */
+
+/* ---- FIR plans: fft_convolve and OverlapSaveConvolver (src/convolution.rs:25-47, :149-270), batched overlap-save.  T = the plan's dtype,
+ * everything is computed in T.  For row r, with L = taps - 1:
+ *   y_r[n] = sum_{k < taps} h_r[k] x_r[n - k]
+ * h is one impulse response for every row (ir_rows 1) or one per row (ir_rows = the batch of every call).  x_r[m] for m < 0 comes from
+ * the row's history: the last L samples seen by earlier streaming calls, zeros after creation and after a reset.
+ *   sgx_fir_process   streaming: n_out = n_samples; afterwards the history is the last L samples of (history | x), so a chunk shorter
+ *                     than L shifts the old history and does not drop it.  Any cut of a signal into calls gives the samples of one
+ *                     call, to rounding.  The history has `batch` rows, fixed by the first streaming call after creation or reset; a
+ *                     later call with another batch is SGX_DIM_MISMATCH (expected / got in the text).
+ *   sgx_fir_convolve  the full, stateless form: the history is taken as zero and left untouched, samples beyond n_samples are zero,
+ *                     n_out = n_samples + taps - 1 (fft_convolve).
+ * The reference ties its FFT size to the caller's block, next_power_of_two(block + taps - 1); a plan here picks its own segment
+ * length P (sgx_fir_fft_size) and step S = P - L (sgx_fir_step) — block_size is a hint it records and the result does not depend on:
+ *   route SGX_FIR_ROUTE_AUTO, taps <= 2049   "k_fir_os": P = next_power_of_two(4 taps) within 256 .. 4096, one fused launch
+ *   otherwise (taps up to 2^19)              "fir_generic": P = next_power_of_two(2 taps), at least 256
+ * The taps are rounded to T first; H = FFT_P(h) / P is built from them in f64 and rounded to T.  `out` must not overlap `x`.
+ * Errors: "impulse response must not be empty" (taps 0; SGX_INVALID_INPUT, the reference's text); more than 2^19 taps SGX_BACKEND.
+ * device -1: the current device, -2: a host-only plan (validation, shapes, route; the compute calls return SGX_BACKEND). */
+typedef struct sgx_fir sgx_fir; /* opaque; same single-caller rule as sgx_mdct */
+enum { SGX_FIR_ROUTE_AUTO = 0, SGX_FIR_ROUTE_GENERIC = 1 };
+sgx_status sgx_fir_create(const double *ir /* [ir_rows][taps] */, size_t taps, size_t ir_rows, size_t block_size, int32_t route, int32_t dtype,
+                          int32_t device, sgx_fir **out);
+void sgx_fir_destroy(sgx_fir *plan);
+/* `batch` rows: row r at x + r * sample_stride (elements of T, sample_stride >= n_samples), n_samples each; out [batch][n_out] T.
+ * out_elems must be batch * n_out (else SGX_DIM_MISMATCH); mem_kind as sgx_execute, `stream` a hipStream_t as its hip_stream (the streams paragraph at the top). */
+sgx_status sgx_fir_process(sgx_fir *plan, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out, size_t out_elems,
+                           int32_t mem_kind, void *stream);
+sgx_status sgx_fir_convolve(sgx_fir *plan, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out, size_t out_elems,
+                            int32_t mem_kind, void *stream);
+/* Zero history and no fixed row count again; the zeroing is enqueued on `stream`. */
+sgx_status sgx_fir_reset(sgx_fir *plan, void *stream);
+/* Pre-sizes the history for `batch` rows, the generic route's scratch for calls (either form) of up to `batch` rows of `n_samples`
+ * samples and, with host_staging, the SGX_MEM_HOST staging, so that those calls do not allocate. */
+sgx_status sgx_fir_reserve(sgx_fir *plan, size_t batch, size_t n_samples, int32_t host_staging);
+size_t sgx_fir_fft_size(const sgx_fir *plan);
+size_t sgx_fir_step(const sgx_fir *plan);
+size_t sgx_fir_taps(const sgx_fir *plan);
+const char *sgx_fir_kernel_name(const sgx_fir *plan); /* "k_fir_os" or "fir_generic" */
+int32_t sgx_fir_device(const sgx_fir *plan);
+const char *sgx_fir_last_error(const sgx_fir *plan); /* NULL plan: the text of the last failed create */
+
+/* ---- deconvolution plans: fft_deconvolve (src/convolution.rs:60-106), batched.  Per row, with n = next_power_of_two(max(n_len, d_len))
+ * and N, D the n-point real transforms of the zero-padded numerator and denominator (the library's R2C / C2R of that length, up to 2^20):
+ *   eps = T(regularization) max_k |D_k|^2;   Q_k = N_k conj(D_k) / (|D_k|^2 + eps), exactly 0 where that denominator is 0;
+ *   y = irfft_n(Q), truncated to n_len - d_len + 1 samples if n_len >= d_len, else to n_len (never below 1).
+ * The denominator is one row for every numerator row (den_rows 1) or one per row (den_rows = batch). */
+typedef struct sgx_deconv sgx_deconv; /* opaque; same single-caller rule as sgx_mdct */
+sgx_status sgx_deconv_create(size_t n_len, size_t d_len, double regularization, int32_t dtype, int32_t device, sgx_deconv **out);
+void sgx_deconv_destroy(sgx_deconv *plan);
+size_t sgx_deconv_output_length(const sgx_deconv *plan);
+/* numerator [batch][n_len], denominator [den_rows][d_len], out [batch][output_length] T, rows contiguous; batch <= 65535. */
+sgx_status sgx_deconv_execute(sgx_deconv *plan, const void *numerator, const void *denominator, size_t batch, size_t den_rows, void *out,
+                              size_t out_elems, int32_t mem_kind, void *stream);
+sgx_status sgx_deconv_reserve(sgx_deconv *plan, size_t batch, size_t den_rows, int32_t host_staging);
+int32_t sgx_deconv_device(const sgx_deconv *plan);
+const char *sgx_deconv_last_error(const sgx_deconv *plan); /* NULL plan: the text of the last failed create */
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db
                         compute_mel_power_spectrogram, compute_mfcc, compute_power_spectrum, compute_rfft, compute_stft,
                         fft_plan_cache_info)
 from .gammatone import GammatonePlan, gammatone_center_frequencies, gammatone_iir_spectrogram
+from .fir import DeconvPlan, FirPlan, OverlapSaveConvolver, fft_convolve, fft_deconvolve
 from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
@@ -57,4 +58,5 @@ __all__ = [
     "IldSpectrogram", "IlrSpectrogram", "BinauralPlan", "compute_itd_spectrogram", "compute_ipd_spectrogram", "compute_ild_spectrogram",
     "compute_ilr_spectrogram", "compute_itd_spectrogram_diff", "compute_ilr_spectrogram_diff",
     "GammatonePlan", "gammatone_iir_spectrogram", "gammatone_center_frequencies",
+    "FirPlan", "OverlapSaveConvolver", "DeconvPlan", "fft_convolve", "fft_deconvolve",
 ]

@@ -20,6 +20,7 @@ AMP_POWER, AMP_MAGNITUDE, AMP_DECIBELS, AMP_COMPLEX = range(4)
 F32, F64 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 DEVICE_CURRENT, DEVICE_HOST_ONLY = -1, -2
+FIR_ROUTE_AUTO, FIR_ROUTE_GENERIC = 0, 1
 
 # every symbol include/spectro_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -38,6 +39,10 @@ SYMBOLS = [
     "sgx_binaural_histogram", "sgx_binaural_reserve", "sgx_binaural_kernel_name", "sgx_binaural_device", "sgx_binaural_last_error",
     "sgx_gammatone_create", "sgx_gammatone_destroy", "sgx_gammatone_output_shape", "sgx_gammatone_execute", "sgx_gammatone_center_frequencies",
     "sgx_gammatone_coefficients", "sgx_gammatone_reserve", "sgx_gammatone_kernel_name", "sgx_gammatone_device", "sgx_gammatone_last_error",
+    "sgx_fir_create", "sgx_fir_destroy", "sgx_fir_process", "sgx_fir_convolve", "sgx_fir_reset", "sgx_fir_reserve", "sgx_fir_fft_size",
+    "sgx_fir_step", "sgx_fir_taps", "sgx_fir_kernel_name", "sgx_fir_device", "sgx_fir_last_error",
+    "sgx_deconv_create", "sgx_deconv_destroy", "sgx_deconv_output_length", "sgx_deconv_execute", "sgx_deconv_reserve",
+    "sgx_deconv_device", "sgx_deconv_last_error",
 ]
 
 
@@ -223,6 +228,31 @@ def lib() -> C.CDLL:
     L.sgx_gammatone_device.restype = C.c_int32
     L.sgx_gammatone_last_error.argtypes = [vp]
     L.sgx_gammatone_last_error.restype = C.c_char_p
+    L.sgx_fir_create.argtypes = [C.POINTER(C.c_double), sz, sz, sz, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sgx_fir_destroy.argtypes = [vp]
+    L.sgx_fir_destroy.restype = None
+    L.sgx_fir_process.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_fir_convolve.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_fir_reset.argtypes = [vp, vp]
+    L.sgx_fir_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    for f in (L.sgx_fir_fft_size, L.sgx_fir_step, L.sgx_fir_taps, L.sgx_deconv_output_length):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_fir_kernel_name.argtypes = [vp]
+    L.sgx_fir_kernel_name.restype = C.c_char_p
+    L.sgx_fir_device.argtypes = [vp]
+    L.sgx_fir_device.restype = C.c_int32
+    L.sgx_fir_last_error.argtypes = [vp]
+    L.sgx_fir_last_error.restype = C.c_char_p
+    L.sgx_deconv_create.argtypes = [sz, sz, C.c_double, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sgx_deconv_destroy.argtypes = [vp]
+    L.sgx_deconv_destroy.restype = None
+    L.sgx_deconv_execute.argtypes = [vp, vp, vp, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_deconv_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_deconv_device.argtypes = [vp]
+    L.sgx_deconv_device.restype = C.c_int32
+    L.sgx_deconv_last_error.argtypes = [vp]
+    L.sgx_deconv_last_error.restype = C.c_char_p
     _lib = L
     return L
 

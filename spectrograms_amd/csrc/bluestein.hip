@@ -30,6 +30,7 @@
 #include <cmath>
 #include <vector>
 
+#include "bs_middle.h"
 #include "reg_radix.h"
 #include "rr_layout.h"
 #include "db_f64.h"
@@ -58,6 +59,10 @@ __device__ __forceinline__ double bs_mul_add_unfused(double w, double p, double 
 __device__ __forceinline__ float bs_db(float p) { return __builtin_log2f(p) * 3.01029995663981195f; }  // as the other f32 kernels
 __device__ __forceinline__ double bs_db(double p) { return db_f64(p); }
 
+#ifdef SGX_BS_STAMPS  // diagnostic build only (tools/stamps_bs.py); the stamp macros are in bs_middle.h
+__device__ unsigned long long g_bs_stamps[16];
+#endif
+
 // ---- the fused kernel ----------------------------------------------------------------------------------------------------
 // One workgroup carries `tile` sequences (frame pairs) through the whole chain in LDS; the only HBM traffic is the samples in
 // and the bins out.
@@ -77,24 +82,6 @@ __device__ __forceinline__ double bs_db(double p) { return db_f64(p); }
 //
 // Deviation from S4, f32 / f64 alike: the kernel multiplies a sample by wc[m] = w[m] conj(c_m), ONE table rounded from f64, rather
 // than by w[m] (rounded) and then by the chirp; the chirp-z result is not bit-comparable with a direct transform either way.
-#ifdef SGX_BS_STAMPS  // diagnostic build only (tools/stamps_bs.py): a wave's cycles per stage of k_bs_fused
-__device__ unsigned long long g_bs_stamps[16];
-#define BS_STAMP(i)                                                                \
-    do {                                                                           \
-        unsigned long long t_;                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        st_acc[i] += t_ - st_prev;                                                 \
-        st_prev = t_;                                                              \
-    } while (0)
-#define BS_STAMP_PARAMS , unsigned long long *st_acc, unsigned long long &st_prev
-#define BS_STAMP_ARGS , st_acc, st_prev
-#else
-#define BS_STAMP(i)
-#define BS_STAMP_PARAMS
-#define BS_STAMP_ARGS
-#endif
 
 struct BsFused {
     const void *x;
@@ -111,94 +98,6 @@ struct BsFused {
     unsigned n_mels, n_out;
 };
 
-// The middle of the convolution, shared by the frame kernel and the complex-sequence kernel: on entry every work item has written
-// its P1 + T1 results to the tile; on return the tile holds conj(T1^-1-input of P1^-1), i.e. what P1^-1's work items read.
-template <typename T, int A_, int B_, int C_>
-__device__ __forceinline__ void bs_middle(typename PairOf<T>::type *buf, unsigned ns, unsigned tid, const typename PairOf<T>::type *tw,
-                                          const typename PairOf<T>::type *bhp BS_STAMP_PARAMS) {
-    typedef typename PairOf<T>::type V;
-    constexpr unsigned A = A_, B = B_, C = C_, N = A * B * C;
-    constexpr int LB = ct_log2_ceil(B);
-    typedef RrLayout<sizeof(V), A_, B_, C_> L;
-    constexpr unsigned RS = L::RS, FS = L::FS;
-    auto wrap = [](unsigned e) { return e & (N - 1); };
-    __syncthreads();
-    BS_STAMP(2);
-    // P2 (+ T2); two-pass splits: P2, product, P2^-1
-    for (unsigned idx = tid; idx < ns * A * C; idx += 256) {
-        const unsigned s = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
-        V *row = buf + (size_t)s * FS + k1 * RS;
-        const unsigned lp = n3 ^ L::k1_mask(k1);
-        V v[B];
-#pragma unroll
-        for (unsigned n2 = 0; n2 < B; ++n2) v[n2] = row[lp ^ L::hi_part(n2)];
-        inreg::MixFft<B, V>::run(v);
-        if constexpr (C > 1) {
-            V q2[LB];
-#pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
-            row[lp ^ L::hi_part(0)] = v[0];
-#pragma unroll
-            for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = inreg::cmulv(v[k2], rr_twiddle<LB>(q2, k2));
-        } else {
-#pragma unroll
-            for (unsigned k2 = 0; k2 < B; ++k2) {  // bin k1 + A k2; the table is [k2][k1]
-                const V y = inreg::cmulv(v[k2], bhp[k2 * A + k1]);
-                v[k2] = (V){y.x, -y.y};
-            }
-            inreg::MixFft<B, V>::run(v);
-#pragma unroll
-            for (unsigned n2 = 0; n2 < B; ++n2) row[lp ^ L::hi_part(n2)] = v[n2];
-        }
-    }
-    BS_STAMP(3);
-    __syncthreads();
-    BS_STAMP(4);
-    if constexpr (C > 1) {
-        // P3, product, P3^-1 (from here on the data is the conjugate of the inverse transform's)
-        for (unsigned idx = tid; idx < ns * A * B; idx += 256) {
-            const unsigned s = idx / (A * B), q = idx % (A * B), k1 = q / B, k2 = q % B;
-            V *row = buf + (size_t)s * FS + k1 * RS;
-            const unsigned lp = L::hi_part(k2) ^ L::k1_mask(k1);
-            V v[C], h[C];
-#pragma unroll
-            for (unsigned k3 = 0; k3 < C; ++k3) h[k3] = bhp[k3 * (A * B) + q];  // bin k1 + A (k2 + B k3); the table is [k3][k1][k2]
-#pragma unroll
-            for (unsigned n3 = 0; n3 < C; ++n3) v[n3] = row[lp ^ n3];
-            inreg::MixFft<C, V>::run(v);
-#pragma unroll
-            for (unsigned k3 = 0; k3 < C; ++k3) {
-                const V y = inreg::cmulv(v[k3], h[k3]);
-                v[k3] = (V){y.x, -y.y};
-            }
-            inreg::MixFft<C, V>::run(v);
-#pragma unroll
-            for (unsigned n3 = 0; n3 < C; ++n3) row[lp ^ n3] = v[n3];
-        }
-        BS_STAMP(5);
-        __syncthreads();
-        BS_STAMP(6);
-        // T2, P2
-        for (unsigned idx = tid; idx < ns * A * C; idx += 256) {
-            const unsigned s = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
-            V *row = buf + (size_t)s * FS + k1 * RS;
-            const unsigned lp = n3 ^ L::k1_mask(k1);
-            V q2[LB];
-#pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
-            V v[B];
-            v[0] = row[lp ^ L::hi_part(0)];
-#pragma unroll
-            for (unsigned k2 = 1; k2 < B; ++k2) v[k2] = inreg::cmulv(row[lp ^ L::hi_part(k2)], rr_twiddle<LB>(q2, k2));
-            inreg::MixFft<B, V>::run(v);
-#pragma unroll
-            for (unsigned n2 = 0; n2 < B; ++n2) row[lp ^ L::hi_part(n2)] = v[n2];
-        }
-        BS_STAMP(7);
-        __syncthreads();
-        BS_STAMP(8);
-    }
-}
 
 template <typename T, int A, int B, int C>
 constexpr unsigned bs_waves() {

@@ -1277,6 +1277,7 @@ InverseRoute inverse_route(const sgx_plan *pl, size_t batch, size_t n_frames, bo
     return r;
 }
 
+constexpr size_t kC2rLds = 144 * 1024;  // LDS of the inverse rows' tile kernels (launch_c2r_frames)
 template <typename T>
 sgx_status inverse_tables(sgx_plan *pl) {
     if (pl->d_itw || pl->d_flag) return SGX_OK;
@@ -1287,6 +1288,15 @@ sgx_status inverse_tables(sgx_plan *pl) {
     }
     sgx_status st = upload<T>(pl, &pl->d_itw, twiddle_vector<T>(unsigned(n), -2.0, unsigned(n)));
     if (st != SGX_OK) return st;
+    // The two lengths whose forward frames fit the LDS radix-2 kernel (half-length complex form) while no tile holds a full-length row
+    // of the inverse (f32 32768, f64 16384): the inverse rows go through global memory, as a K_BIGFFT plan's do.  (Before: sgx_istft
+    // and sgx_c2r returned "n_fft too large for the on-chip frame tile" there.)
+    if (c2r_tile_for(unsigned(n), pl->dtype, kC2rLds) == 0 && big_supported(n)) {
+        BigHost h;
+        if (!big_host_tables(unsigned(n), h)) return set_err(pl, SGX_INTERNAL, "Internal error: no global-memory transform for the inverse rows");
+        SGX_HIP(pl, big_upload(h, pl->dtype, pl->big));
+        if ((st = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return st;  // one sequence: sgx_c2r
+    }
     // Even lengths whose rows have neither a register-tiled split (n / 2) nor a chirp-z convolution of their own in LDS (f64 above
     // 4096, f32 above 8192) invert through the chirp-z kernel in half-length complex form: tables of length n / 2.  (Before: the
     // direct sum — f64 n_fft 6000, 64 x 10 s: 1.27 s.)
@@ -1326,7 +1336,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
     c.in_img = (unsigned long long)pl->nb_fft * n_frames;
     if (frame_fast) { c.in_ks = n_frames; c.in_rs = 1; c.k_fast = 0; }  // [bin][frame] (StftResult layout, S9)
     else { c.in_ks = 1; c.in_rs = pl->nb_fft; c.k_fast = 1; }
-    if (pl->kind == K_BIGFFT) {  // rows through global memory (two frames per complex sequence, the forward engine behind conj)
+    if (pl->kind == K_BIGFFT || pl->big.M) {  // rows through global memory (two frames per complex sequence, the forward engine behind conj)
         c.scale = inverse_scale(pl);
         c.win = win;
         c.bad_flag = (unsigned *)pl->d_flag;
@@ -1336,7 +1346,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
         *route = "big";
         return SGX_OK;
     }
-    c.tile = c2r_tile_for(n, pl->dtype, 144 * 1024);
+    c.tile = c2r_tile_for(n, pl->dtype, kC2rLds);
     if (c.tile == 0) return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
     c.tiles = unsigned((n_frames + c.tile - 1) / c.tile);
     c.tw = pl->d_itw;
@@ -1893,7 +1903,7 @@ sgx_status sgx_reserve(sgx_plan *plan, size_t batch, size_t n_samples, int32_t h
     if (!inverse && plan->split_bank &&
         (st = grow(plan, &plan->d_pwbuf, &plan->d_pwbuf_bytes, batch * size_t(plan->nb_fft) * nf * plan->elem)) != SGX_OK)
         return st;
-    if (plan->kind == K_BIGFFT &&
+    if ((plan->kind == K_BIGFFT || (inverse && plan->big.M)) &&
         (st = grow(plan, &plan->d_big, &plan->d_big_bytes, big_scratch_bytes(plan->big, plan->dtype, batch * ((nf + 1) / 2)))) != SGX_OK)
         return st;
     if (inverse) {  // sgx_istft of `batch` spectra whose frame count is that of n_samples-long signals
