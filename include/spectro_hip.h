@@ -32,7 +32,7 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
@@ -527,6 +527,41 @@ sgx_status sgx_deconv_execute(sgx_deconv *plan, const void *numerator, const voi
 sgx_status sgx_deconv_reserve(sgx_deconv *plan, size_t batch, size_t den_rows, int32_t host_staging);
 int32_t sgx_deconv_device(const sgx_deconv *plan);
 const char *sgx_deconv_last_error(const sgx_deconv *plan); /* NULL plan: the text of the last failed create */
+
+/* ---- minimum-phase plans: minimum_phase / minimum_phase_with (src/min_phase.rs:55-141), batched.  The real-cepstrum method, per row,
+ * with n = next_power_of_two(taps * max(oversample, 1)) (sgx_minphase_fft_size):
+ *   H = FFT_n(h zero-padded);   eps = 1e-20 max_k |H_k|^2, or 1e-300 if that maximum is 0;   L_k = 0.5 ln(|H_k|^2 + eps);
+ *   c = IFFT_n(L), folded: c_0 and c_{n/2} kept, c_1 .. c_{n/2-1} doubled, everything above n/2 dropped;
+ *   C = FFT_n(folded c);   Hmin_k = exp(Re C_k) (cos Im C_k + i sin Im C_k);   y = Re IFFT_n(Hmin),
+ * and the output row is its first sgx_minphase_output_length = min(out_len, n) samples.  minimum_phase is out_len = taps, oversample 8.
+ * One deliberate difference from the reference, which computes in the sample type: the arithmetic is f64 for BOTH dtypes.  T = the
+ * plan's dtype is the type of the input and output rows only; every transform, the log, the exp and the sin / cos are f64, and the
+ * result is rounded to T once.  (In f32 the log amplifies the forward transform's rounding at every spectral null: on linear-phase
+ * low-passes, the function's main input, an f32 pipeline is off by 5e-4 of the peak tap at 64 taps and by 0.6 at 4096.)
+ *   route SGX_MINPHASE_ROUTE_AUTO, n <= 4096   "k_minphase": one launch, one workgroup per row, the row in LDS for all four transforms
+ *   otherwise (n up to 2^20)                   "minphase_generic": the library's f64 R2C / C2R of length n (an internal plan, as the
+ *                                              deconvolution plans) with elementwise kernels between them; SGX_MINPHASE_ROUTE_GENERIC
+ *                                              asks for it at any n (the internal plans transform every n from 1 up: no lower limit)
+ * Errors: "impulse response must not be empty" (taps 0), "out_len must be greater than zero" (both SGX_INVALID_INPUT, the reference's
+ * texts); n above 2^20 SGX_BACKEND.  device -1: the current device, -2: a host-only plan (validation, shapes, route; compute and
+ * reserve return SGX_BACKEND). */
+typedef struct sgx_minphase sgx_minphase; /* opaque; same single-caller rule as sgx_mdct */
+enum { SGX_MINPHASE_ROUTE_AUTO = 0, SGX_MINPHASE_ROUTE_GENERIC = 1 };
+sgx_status sgx_minphase_create(size_t taps, size_t out_len, size_t oversample, int32_t route, int32_t dtype, int32_t device, sgx_minphase **out);
+void sgx_minphase_destroy(sgx_minphase *plan);
+/* ir [batch][taps] T, out [batch][output_length] T, rows contiguous; batch <= 65535; `out` must not overlap `ir`.  out_elems must be
+ * batch * output_length (else SGX_DIM_MISMATCH); mem_kind as sgx_execute, `stream` a hipStream_t as its hip_stream (the streams
+ * paragraph at the top holds for this call too: one operation of that stream, capturable once reserved). */
+sgx_status sgx_minphase_execute(sgx_minphase *plan, const void *ir, size_t batch, void *out, size_t out_elems, int32_t mem_kind, void *stream);
+/* Pre-sizes the generic route's scratch for calls of up to `batch` rows and, with host_staging, the SGX_MEM_HOST staging, so that
+ * those calls do not allocate (the fused route needs no scratch). */
+sgx_status sgx_minphase_reserve(sgx_minphase *plan, size_t batch, int32_t host_staging);
+size_t sgx_minphase_fft_size(const sgx_minphase *plan);
+size_t sgx_minphase_output_length(const sgx_minphase *plan);
+size_t sgx_minphase_taps(const sgx_minphase *plan);
+const char *sgx_minphase_kernel_name(const sgx_minphase *plan); /* "k_minphase" or "minphase_generic" */
+int32_t sgx_minphase_device(const sgx_minphase *plan);
+const char *sgx_minphase_last_error(const sgx_minphase *plan); /* NULL plan: the text of the last failed create */
 
 #ifdef __cplusplus
 }

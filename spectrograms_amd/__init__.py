@@ -24,6 +24,7 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db
 from .gammatone import GammatonePlan, gammatone_center_frequencies, gammatone_iir_spectrogram
 from .fir import DeconvPlan, FirPlan, OverlapSaveConvolver, fft_convolve, fft_deconvolve
 from .mdct import MdctParams, MdctPlan, imdct, mdct
+from .minphase import MinPhasePlan, minimum_phase, minimum_phase_with
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
@@ -59,4 +60,5 @@ __all__ = [
     "compute_ilr_spectrogram", "compute_itd_spectrogram_diff", "compute_ilr_spectrogram_diff",
     "GammatonePlan", "gammatone_iir_spectrogram", "gammatone_center_frequencies",
     "FirPlan", "OverlapSaveConvolver", "DeconvPlan", "fft_convolve", "fft_deconvolve",
+    "MinPhasePlan", "minimum_phase", "minimum_phase_with",
 ]

@@ -21,6 +21,7 @@ F32, F64 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 DEVICE_CURRENT, DEVICE_HOST_ONLY = -1, -2
 FIR_ROUTE_AUTO, FIR_ROUTE_GENERIC = 0, 1
+MINPHASE_ROUTE_AUTO, MINPHASE_ROUTE_GENERIC = 0, 1
 
 # every symbol include/spectro_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -43,6 +44,8 @@ SYMBOLS = [
     "sgx_fir_step", "sgx_fir_taps", "sgx_fir_kernel_name", "sgx_fir_device", "sgx_fir_last_error",
     "sgx_deconv_create", "sgx_deconv_destroy", "sgx_deconv_output_length", "sgx_deconv_execute", "sgx_deconv_reserve",
     "sgx_deconv_device", "sgx_deconv_last_error",
+    "sgx_minphase_create", "sgx_minphase_destroy", "sgx_minphase_execute", "sgx_minphase_reserve", "sgx_minphase_fft_size",
+    "sgx_minphase_output_length", "sgx_minphase_taps", "sgx_minphase_kernel_name", "sgx_minphase_device", "sgx_minphase_last_error",
 ]
 
 
@@ -253,6 +256,20 @@ def lib() -> C.CDLL:
     L.sgx_deconv_device.restype = C.c_int32
     L.sgx_deconv_last_error.argtypes = [vp]
     L.sgx_deconv_last_error.restype = C.c_char_p
+    L.sgx_minphase_create.argtypes = [sz, sz, sz, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sgx_minphase_destroy.argtypes = [vp]
+    L.sgx_minphase_destroy.restype = None
+    L.sgx_minphase_execute.argtypes = [vp, vp, sz, vp, sz, C.c_int32, vp]
+    L.sgx_minphase_reserve.argtypes = [vp, sz, C.c_int32]
+    for f in (L.sgx_minphase_fft_size, L.sgx_minphase_output_length, L.sgx_minphase_taps):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_minphase_kernel_name.argtypes = [vp]
+    L.sgx_minphase_kernel_name.restype = C.c_char_p
+    L.sgx_minphase_device.argtypes = [vp]
+    L.sgx_minphase_device.restype = C.c_int32
+    L.sgx_minphase_last_error.argtypes = [vp]
+    L.sgx_minphase_last_error.restype = C.c_char_p
     _lib = L
     return L
 
