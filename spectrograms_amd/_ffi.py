@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SGX_LIB_PATH lets kernel A/B experiments (tools/ablate.sh) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("SGX_LIB_PATH") or os.path.join(_PKG, "libspectro_hip.so")
@@ -272,6 +274,46 @@ def lib() -> C.CDLL:
     L.sgx_minphase_last_error.restype = C.c_char_p
     _lib = L
     return L
+
+
+def np_dtype(code: int):
+    """numpy type of a dtype code (F32 / F64)."""
+    return np.float32 if code == F32 else np.float64
+
+
+class NativeHandle:
+    """One opaque plan of a satellite family of the C ABI.  A subclass names the family's symbol prefix (`_prefix`, e.g. "sgx_mdct"),
+    sets `_lib` and `_dt` (the plan's dtype code) and passes its create call's status and handle to `_create`; every later status
+    goes through `_check`.  Creation errors are read from <prefix>_last_error(NULL), call errors from the plan."""
+
+    _prefix = ""
+    _h = None
+
+    def _last_error(self, handle) -> str:
+        return (getattr(self._lib, self._prefix + "_last_error")(handle) or b"").decode()
+
+    def _create(self, status: int, handle) -> None:
+        if status:
+            raise _ERR.get(status, InternalError)(self._last_error(None))
+        self._h = handle
+
+    def _check(self, status: int) -> None:
+        if status:
+            raise _ERR.get(status, InternalError)(self._last_error(self._h))
+
+    def __del__(self):
+        if self._h:
+            getattr(self._lib, self._prefix + "_destroy")(self._h)
+            self._h = None
+
+    @property
+    def _np(self):
+        return np_dtype(self._dt)
+
+    @property
+    def _tdt(self):
+        import torch
+        return torch.float32 if self._dt == F32 else torch.float64
 
 
 def raise_status(status: int, plan=None) -> None:

@@ -125,32 +125,21 @@ class ILRSpectrogramParams(_BinauralParams):
         super().__init__(spectrogram_params, 1700.0 if start_freq is None else start_freq, 4600.0 if end_freq is None else end_freq)
 
 
-class BinauralPlan:
+class BinauralPlan(_ffi.NativeHandle):
     """One sgx_binaural (params + dtype + device).  Not thread-safe, like the reference's `&mut self` plans."""
+
+    _prefix = "sgx_binaural"
 
     def __init__(self, params: _BinauralParams, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT):
         self._lib = _ffi.lib()
         self.params = params
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         sp, self._cw = _stft_struct(params.spectrogram_params, self._dt, int(device))
         bp = params._c()
         h = C.c_void_p()
         st = self._lib.sgx_binaural_create(C.byref(sp), C.byref(bp), C.byref(h))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_binaural_last_error(None) or b"").decode())
-        self._h = h
+        self._create(st, h)
         self._device = int(self._lib.sgx_binaural_device(h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_binaural_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_binaural_last_error(self._h) or b"").decode())
 
     @property
     def device(self) -> int:
@@ -218,7 +207,7 @@ class BinauralPlan:
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
     def _tensor(self, t, what: str, ndim: int):
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         if not t.is_cuda or t.device.index != self._device:
             raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
         if t.dtype != tdt or not t.is_contiguous():

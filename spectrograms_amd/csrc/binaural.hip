@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "binaural_kind.h"
-#include "sgx_internal.h"
+#include "plan_host.h"
 
 using namespace sgx;
 using namespace sgx::binaural;
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void k_binaural_hist(const T *__restrict__ val
 }  // namespace
 
 struct sgx_binaural {
-    sgx_plan *stft = nullptr;  // the complex STFT of both channels (SGX_AMP_COMPLEX); host-only when the binaural plan is
+    PlanHandle stft;  // the complex STFT of both channels (SGX_AMP_COMPLEX); host-only when the binaural plan is
     sgx_binaural_params bp{};
     int dtype = SGX_F32;
     size_t elem = 4;
@@ -144,39 +144,15 @@ struct sgx_binaural {
     size_t start_bin = 0, stop_bin = 0;
     std::string route;
     bool fused = false;  // f32 n_fft 1024 on the tuned kernel: both channels in one launch (launch_r32x16_binaural)
-    void *d_spec = nullptr, *d_in = nullptr, *d_out = nullptr;  // chunk spectra [2][cb][nb][nf] complex; SGX_MEM_HOST staging
-    size_t spec_bytes = 0, in_bytes = 0, out_bytes = 0;
+    DevBuf d_spec, d_in, d_out;  // chunk spectra [2][cb][nb][nf] complex; SGX_MEM_HOST staging
     mutable std::string err;
 };
 
 namespace {
 
-thread_local std::string g_bin_err;
-
-sgx_status bfail(const sgx_binaural *p, sgx_status st, const std::string &m) {
-    if (p) p->err = m; else g_bin_err = m;
-    return st;
-}
-#define BN_HIP(plan, call)                                                                                            \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess)                                                                                         \
-            return bfail(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-sgx_status bgrow(sgx_binaural *p, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) BN_HIP(p, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    BN_HIP(p, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
-
 // the inner plan's failure, re-reported on the binaural plan
 sgx_status from_stft(sgx_binaural *p, sgx_status st) {
-    return bfail(p, st, sgx_last_error(p->stft) ? sgx_last_error(p->stft) : "");
+    return fail(p, st, sgx_last_error(p->stft.get()) ? sgx_last_error(p->stft.get()) : "");
 }
 
 size_t chunk_rows(const sgx_binaural *p, size_t batch, size_t nf) {
@@ -209,7 +185,7 @@ hipError_t launch_epi(const sgx_binaural *p, const void *spec, void *out, unsign
 // fused route: the tuned kernel's tables from the complex plan, one launch for the whole batch; false: the shape is not the kernel's
 bool fused_args(const sgx_binaural *p, StftArgs &a, const void *left, const void *right, size_t batch, size_t n_samples, size_t stride,
                 size_t nf, void *out) {
-    const sgx_plan *pl = p->stft;
+    const sgx_plan *pl = p->stft.get();
     std::memset(&a, 0, sizeof(a));
     a.x = left;
     a.x2 = right;
@@ -247,24 +223,24 @@ sgx_status run_dev(sgx_binaural *p, const void *left, const void *right, size_t 
     if (p->fused) {
         StftArgs a;
         if (fused_args(p, a, left, right, batch, n_samples, stride, nf, out)) {
-            BN_HIP(p, launch_r32x16_binaural(a, s));
+            SGX_TRY_HIP(p, launch_r32x16_binaural(a, s));
             return SGX_OK;
         }
     }
     const size_t cb = chunk_rows(p, batch, nf), spec_elems = cb * p->nb * nf * 2u;
     sgx_status st;
-    if ((st = bgrow(p, &p->d_spec, &p->spec_bytes, 2u * spec_elems * p->elem)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_spec, 2u * spec_elems * p->elem)) != SGX_OK) return st;
     const size_t n_bins = p->stop_bin - p->start_bin;
     for (size_t b0 = 0; b0 < batch; b0 += cb) {
         const size_t n = std::min(cb, batch - b0), elems = n * p->nb * nf * 2u;
-        unsigned char *specL = static_cast<unsigned char *>(p->d_spec), *specR = specL + n * p->nb * nf * 2u * p->elem;
+        unsigned char *specL = p->d_spec.as<unsigned char>(), *specR = specL + n * p->nb * nf * 2u * p->elem;
         const size_t in_off = b0 * stride * p->elem;
-        if ((st = sgx_execute(p->stft, static_cast<const unsigned char *>(left) + in_off, n, n_samples, stride, specL, elems, SGX_MEM_DEVICE, s)) != SGX_OK)
+        if ((st = sgx_execute(p->stft.get(), static_cast<const unsigned char *>(left) + in_off, n, n_samples, stride, specL, elems, SGX_MEM_DEVICE, s)) != SGX_OK)
             return from_stft(p, st);
-        if ((st = sgx_execute(p->stft, static_cast<const unsigned char *>(right) + in_off, n, n_samples, stride, specR, elems, SGX_MEM_DEVICE, s)) != SGX_OK)
+        if ((st = sgx_execute(p->stft.get(), static_cast<const unsigned char *>(right) + in_off, n, n_samples, stride, specR, elems, SGX_MEM_DEVICE, s)) != SGX_OK)
             return from_stft(p, st);
         void *o = static_cast<unsigned char *>(out) + b0 * n_bins * nf * p->elem;
-        BN_HIP(p, p->dtype == SGX_F64 ? launch_epi<double>(p, specL, o, unsigned(n), unsigned(nf), s)
+        SGX_TRY_HIP(p, p->dtype == SGX_F64 ? launch_epi<double>(p, specL, o, unsigned(n), unsigned(nf), s)
                                       : launch_epi<float>(p, specL, o, unsigned(n), unsigned(nf), s));
     }
     return SGX_OK;
@@ -287,9 +263,9 @@ extern "C" {
 
 sgx_status sgx_binaural_create(const sgx_params *stft, const sgx_binaural_params *bp, sgx_binaural **out) {
     if (out) *out = nullptr;
-    if (!out || !stft || !bp) return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!out || !stft || !bp) return fail<sgx_binaural>(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
     if (bp->kind < SGX_BINAURAL_ITD || bp->kind > SGX_BINAURAL_ILR)
-        return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: unknown binaural kind " + std::to_string(bp->kind));
+        return fail<sgx_binaural>(nullptr, SGX_INVALID_INPUT, "Invalid input: unknown binaural kind " + std::to_string(bp->kind));
     // the STFT fields only: a linear complex plan of the same framing, window and type
     sgx_params sp = *stft;
     sp.freq_scale = SGX_FREQ_LINEAR;
@@ -297,35 +273,25 @@ sgx_status sgx_binaural_create(const sgx_params *stft, const sgx_binaural_params
     sp.has_log_params = 0;
     sp.n_mels = 0;
     sp.n_mfcc = 0;
-    sgx_plan *inner = nullptr;
-    sgx_status st = sgx_plan_create(&sp, &inner);
-    if (st != SGX_OK) return bfail(nullptr, st, sgx_last_create_error() ? sgx_last_create_error() : "");
+    sgx_plan *raw = nullptr;
+    sgx_status st = sgx_plan_create(&sp, &raw);
+    PlanHandle inner(raw);  // destroyed with every refusal below
+    if (st != SGX_OK) return fail<sgx_binaural>(nullptr, st, sgx_last_create_error() ? sgx_last_create_error() : "");
     std::string msg;
-    if ((st = check_freqs(sp, *bp, msg)) != SGX_OK) {
-        sgx_plan_destroy(inner);
-        return bfail(nullptr, st, msg);
-    }
-    if (bp->magphase_power == 0) {  // NonZeroUsize in the reference (the Python binding maps 0 to 1)
-        sgx_plan_destroy(inner);
-        return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: magphase_power must be >= 1");
-    }
+    if ((st = check_freqs(sp, *bp, msg)) != SGX_OK) return fail<sgx_binaural>(nullptr, st, msg);
+    if (bp->magphase_power == 0)  // NonZeroUsize in the reference (the Python binding maps 0 to 1)
+        return fail<sgx_binaural>(nullptr, SGX_INVALID_INPUT, "Invalid input: magphase_power must be >= 1");
     const double bw = sp.sample_rate_hz / double(sp.n_fft);
     const double sb = std::round(bp->start_freq / bw), eb = std::round(bp->end_freq / bw);  // (f / bw).round() as usize
     const size_t nb = sp.n_fft / 2u + 1u;
-    if (!(eb > sb) || eb > double(nb)) {  // an empty band: the reference panics at NonEmptyVec::new (:550)
-        sgx_plan_destroy(inner);
-        return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: Frequency range should have at least one bin");
-    }
+    if (!(eb > sb) || eb > double(nb))  // an empty band: the reference panics at NonEmptyVec::new (:550)
+        return fail<sgx_binaural>(nullptr, SGX_INVALID_INPUT, "Invalid input: Frequency range should have at least one bin");
     sgx_binaural *p = new (std::nothrow) sgx_binaural();
-    if (!p) {
-        sgx_plan_destroy(inner);
-        return bfail(nullptr, SGX_INTERNAL, "Internal error: out of memory");
-    }
-    p->stft = inner;
+    if (!p) return fail<sgx_binaural>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->bp = *bp;
     p->dtype = sp.dtype;
-    p->elem = sp.dtype == SGX_F64 ? 8u : 4u;
-    p->device = sgx_plan_device(inner);
+    p->elem = elem_size(sp.dtype);
+    p->device = sgx_plan_device(inner.get());
     p->sr = sp.sample_rate_hz;
     p->bw = bw;
     p->n_fft = sp.n_fft;
@@ -338,29 +304,24 @@ sgx_status sgx_binaural_create(const sgx_params *stft, const sgx_binaural_params
 #else
     p->fused = sp.dtype == SGX_F32 && sp.n_fft == 1024u && inner->kind == K_R32X16_F32;
 #endif
-    p->route = p->fused ? std::string("r32x16_binaural_f32") : std::string("binaural_epilogue/") + sgx_kernel_name(inner);
+    p->route = p->fused ? std::string("r32x16_binaural_f32") : std::string("binaural_epilogue/") + sgx_kernel_name(inner.get());
+    p->stft = std::move(inner);
     *out = p;
     return SGX_OK;
 }
 
 void sgx_binaural_destroy(sgx_binaural *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        void *bufs[] = {p->d_spec, p->d_in, p->d_out};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-    }
-    sgx_plan_destroy(p->stft);
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
     delete p;
 }
 
 sgx_status sgx_binaural_output_shape(const sgx_binaural *p, size_t n_samples, size_t *start_bin, size_t *n_bins, size_t *n_frames) {
-    if (!p || !start_bin || !n_bins || !n_frames) return bfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !start_bin || !n_bins || !n_frames) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     size_t nb, nf;
-    const sgx_status st = sgx_output_shape(p->stft, n_samples, &nb, &nf);
-    if (st != SGX_OK) return bfail(p, st, sgx_last_error(p->stft) ? sgx_last_error(p->stft) : "");
+    const sgx_status st = sgx_output_shape(p->stft.get(), n_samples, &nb, &nf);
+    if (st != SGX_OK) return fail(p, st, sgx_last_error(p->stft.get()) ? sgx_last_error(p->stft.get()) : "");
     *start_bin = p->start_bin;
     *n_bins = p->stop_bin - p->start_bin;
     *n_frames = nf;
@@ -368,7 +329,7 @@ sgx_status sgx_binaural_output_shape(const sgx_binaural *p, size_t n_samples, si
 }
 
 sgx_status sgx_binaural_axes(const sgx_binaural *p, size_t n_frames, double *freqs, double *times) {
-    if (!p) return bfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     if (freqs)  // bin as f64 * bin_width (:541-545)
         for (size_t k = p->start_bin; k < p->stop_bin; ++k) freqs[k - p->start_bin] = double(k) * p->bw;
     if (times)  // frame as f64 * hop_size / sample_rate (:548-553)
@@ -378,63 +339,63 @@ sgx_status sgx_binaural_axes(const sgx_binaural *p, size_t n_frames, double *fre
 
 sgx_status sgx_binaural_execute(sgx_binaural *p, const void *left, const void *right, size_t batch, size_t n_samples, size_t sample_stride,
                                 void *out, size_t out_elems, int32_t mem_kind, void *hip_stream) {
-    if (!p) return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!left || !right || !out) return bfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || n_samples == 0) return bfail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
-    if (sample_stride < n_samples) return bfail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
-    if (batch > 0xffffffffull) return bfail(p, SGX_INVALID_INPUT, "Invalid input: batch too large");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!left || !right || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || n_samples == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
+    if (sample_stride < n_samples) return fail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
+    if (batch > 0xffffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch too large");
     size_t sb, n_bins, nf;
     sgx_status st = sgx_binaural_output_shape(p, n_samples, &sb, &n_bins, &nf);
     if (st != SGX_OK) return st;
-    if (nf > 0x7fffffffull) return bfail(p, SGX_INVALID_INPUT, "Invalid input: too many frames");
+    if (nf > 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: too many frames");
     const size_t expected = batch * n_bins * nf;
     if (out_elems != expected)
-        return bfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return bfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return bfail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+        return dim_mismatch(p, expected, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard dg;
-    BN_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     if (mem_kind == SGX_MEM_DEVICE) return run_dev(p, left, right, batch, n_samples, sample_stride, nf, out, s);
     // host pointers: plan-owned staging (both channels' rows, then the map), synchronous
     const size_t in_bytes = ((batch - 1) * sample_stride + n_samples) * p->elem, out_bytes = expected * p->elem;
-    if ((st = bgrow(p, &p->d_in, &p->in_bytes, 2u * in_bytes)) != SGX_OK) return st;
-    if ((st = bgrow(p, &p->d_out, &p->out_bytes, out_bytes)) != SGX_OK) return st;
-    unsigned char *dl = static_cast<unsigned char *>(p->d_in), *dr = dl + in_bytes;
-    BN_HIP(p, hipMemcpyAsync(dl, left, in_bytes, hipMemcpyHostToDevice, s));
-    BN_HIP(p, hipMemcpyAsync(dr, right, in_bytes, hipMemcpyHostToDevice, s));
+    if ((st = grow(p, p->d_in, 2u * in_bytes)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_out, out_bytes)) != SGX_OK) return st;
+    unsigned char *dl = p->d_in.as<unsigned char>(), *dr = dl + in_bytes;
+    SGX_TRY_HIP(p, hipMemcpyAsync(dl, left, in_bytes, hipMemcpyHostToDevice, s));
+    SGX_TRY_HIP(p, hipMemcpyAsync(dr, right, in_bytes, hipMemcpyHostToDevice, s));
     if ((st = run_dev(p, dl, dr, batch, n_samples, sample_stride, nf, p->d_out, s)) != SGX_OK) return st;
-    BN_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    BN_HIP(p, hipStreamSynchronize(s));
+    SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(p, hipStreamSynchronize(s));
     return SGX_OK;
 }
 
 sgx_status sgx_binaural_histogram(sgx_binaural *p, const void *values, size_t batch, size_t n_frames, size_t num_bins, double lo, double hi,
                                   int32_t exponent, int32_t normalize, double *out, size_t out_elems, int32_t mem_kind, void *hip_stream) {
-    if (!p) return bfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!values || !out) return bfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || n_frames == 0) return bfail(p, SGX_INVALID_INPUT, "Invalid input: values must be non-empty");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!values || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || n_frames == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: values must be non-empty");
     if (num_bins == 0 || num_bins > kHistMaxBins)
-        return bfail(p, SGX_INVALID_INPUT, "Invalid input: num_bins must be in 1.." + std::to_string(kHistMaxBins));
-    if (batch > 0xffffffffull || n_frames > 0x7fffffffull) return bfail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
+        return fail(p, SGX_INVALID_INPUT, "Invalid input: num_bins must be in 1.." + std::to_string(kHistMaxBins));
+    if (batch > 0xffffffffull || n_frames > 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
     const size_t n_rows = p->stop_bin - p->start_bin, expected = batch * num_bins * n_frames;
     if (out_elems != expected)
-        return bfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return bfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return bfail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+        return dim_mismatch(p, expected, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard dg;
-    BN_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     const size_t in_bytes = batch * n_rows * n_frames * p->elem, out_bytes = expected * 8u;
     const void *vin = values;
     double *vout = out;
     sgx_status st;
     if (mem_kind == SGX_MEM_HOST) {
-        if ((st = bgrow(p, &p->d_in, &p->in_bytes, in_bytes)) != SGX_OK) return st;
-        if ((st = bgrow(p, &p->d_out, &p->out_bytes, out_bytes)) != SGX_OK) return st;
-        BN_HIP(p, hipMemcpyAsync(p->d_in, values, in_bytes, hipMemcpyHostToDevice, s));
+        if ((st = grow(p, p->d_in, in_bytes)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, out_bytes)) != SGX_OK) return st;
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in, values, in_bytes, hipMemcpyHostToDevice, s));
         vin = p->d_in;
-        vout = static_cast<double *>(p->d_out);
+        vout = p->d_out.as<double>();
     }
     // frames per workgroup: up to 64, as many as one column block of counts in kHistLdsBytes allows
     const unsigned nbins = unsigned(num_bins);
@@ -443,38 +404,38 @@ sgx_status sgx_binaural_histogram(sgx_binaural *p, const void *values, size_t ba
     const dim3 grid(unsigned((n_frames + fb - 1) / fb), unsigned(std::min<size_t>(batch, 65535)));
     const double width = (hi - lo) / double(num_bins);
     if (p->dtype == SGX_F64) {
-        BN_HIP(p, set_max_dynamic_lds((const void *)k_binaural_hist<double>, int(kHistLdsBytes)));
+        SGX_TRY_HIP(p, set_max_dynamic_lds((const void *)k_binaural_hist<double>, int(kHistLdsBytes)));
         hipLaunchKernelGGL(k_binaural_hist<double>, grid, dim3(256), lds, s, static_cast<const double *>(vin), vout, unsigned(batch),
                            unsigned(n_rows), unsigned(n_frames), nbins, fb, lo, hi, width, exponent, normalize);
     } else {
-        BN_HIP(p, set_max_dynamic_lds((const void *)k_binaural_hist<float>, int(kHistLdsBytes)));
+        SGX_TRY_HIP(p, set_max_dynamic_lds((const void *)k_binaural_hist<float>, int(kHistLdsBytes)));
         hipLaunchKernelGGL(k_binaural_hist<float>, grid, dim3(256), lds, s, static_cast<const float *>(vin), vout, unsigned(batch),
                            unsigned(n_rows), unsigned(n_frames), nbins, fb, lo, hi, width, exponent, normalize);
     }
-    BN_HIP(p, hipGetLastError());
+    SGX_TRY_HIP(p, hipGetLastError());
     if (mem_kind == SGX_MEM_HOST) {
-        BN_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-        BN_HIP(p, hipStreamSynchronize(s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        SGX_TRY_HIP(p, hipStreamSynchronize(s));
     }
     return SGX_OK;
 }
 
 sgx_status sgx_binaural_reserve(sgx_binaural *p, size_t batch, size_t n_samples, int32_t host_staging) {
-    if (!p || batch == 0) return bfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
-    if (p->device == -2) return bfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+    if (!p || batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     size_t sb, n_bins, nf;
     sgx_status st = sgx_binaural_output_shape(p, n_samples, &sb, &n_bins, &nf);
     if (st != SGX_OK) return st;
     const size_t cb = chunk_rows(p, batch, nf);
     DeviceGuard dg;
-    BN_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     if (!p->fused) {  // (the fused route needs no scratch)
-        if ((st = sgx_reserve(p->stft, cb, n_samples, 0, 0)) != SGX_OK) return from_stft(p, st);
-        if ((st = bgrow(p, &p->d_spec, &p->spec_bytes, 2u * cb * p->nb * nf * 2u * p->elem)) != SGX_OK) return st;
+        if ((st = sgx_reserve(p->stft.get(), cb, n_samples, 0, 0)) != SGX_OK) return from_stft(p, st);
+        if ((st = grow(p, p->d_spec, 2u * cb * p->nb * nf * 2u * p->elem)) != SGX_OK) return st;
     }
     if (host_staging) {
-        if ((st = bgrow(p, &p->d_in, &p->in_bytes, 2u * batch * n_samples * p->elem)) != SGX_OK) return st;
-        if ((st = bgrow(p, &p->d_out, &p->out_bytes, batch * n_bins * nf * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in, 2u * batch * n_samples * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, batch * n_bins * nf * p->elem)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
@@ -483,6 +444,6 @@ const char *sgx_binaural_kernel_name(const sgx_binaural *p) { return p ? p->rout
 
 int32_t sgx_binaural_device(const sgx_binaural *p) { return p ? p->device : -2; }
 
-const char *sgx_binaural_last_error(const sgx_binaural *p) { return p ? p->err.c_str() : g_bin_err.c_str(); }
+const char *sgx_binaural_last_error(const sgx_binaural *p) { return p ? p->err.c_str() : create_err<sgx_binaural>().c_str(); }
 
 }  // extern "C"

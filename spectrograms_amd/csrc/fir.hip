@@ -42,7 +42,7 @@
 #include "bs_middle.h"
 #include "reg_radix.h"
 #include "rr_layout.h"
-#include "sgx_internal.h"
+#include "plan_host.h"
 #include "xcd_map.h"
 
 using namespace sgx;
@@ -285,7 +285,6 @@ unsigned grid_for(unsigned long long total) {
     return (unsigned)std::max(1ull, std::min(g, 1ull << 20));
 }
 
-size_t esize(int dtype) { return dtype == SGX_F64 ? 8 : 4; }
 size_t next_pow2(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 // FFT_P of a real sequence on the host: iterative radix-2, f64
@@ -325,12 +324,10 @@ struct sgx_fir {
     bool fused = false;
     unsigned fa = 0, fb = 0, fc = 0;
     std::vector<double> ir;  // [ir_rows][taps], rounded to T
-    void *d_H = nullptr, *d_tw = nullptr;
+    DevBuf d_H, d_tw;
     BigDev big;  // generic route above 4096 points
-    void *d_big = nullptr, *d_seq = nullptr, *d_spec = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t big_bytes = 0, seq_bytes = 0, spec_bytes = 0, in_bytes = 0, out_bytes = 0;
-    void *d_hist[2] = {nullptr, nullptr};  // [rows][taps - 1] T: the history, and where k_fir_hist writes the next one
-    size_t hist_bytes = 0;
+    DevBuf d_big, d_seq, d_spec, d_in, d_out;
+    DevBuf d_hist[2];  // [rows][taps - 1] T: the history, and where k_fir_hist writes the next one
     size_t rows = 0;  // rows of the history, fixed by the first streaming call after creation / reset (0: not fixed)
     mutable std::string err;
 };
@@ -340,58 +337,12 @@ struct sgx_deconv {
     double reg = 0.0;
     int dtype = SGX_F32, device = -1;
     size_t elem = 4;
-    sgx_plan *fft = nullptr;  // one frame of n samples per row: sgx_execute = batched R2C, sgx_istft = batched C2R
-    void *d_num = nullptr, *d_den = nullptr, *d_nspec = nullptr, *d_dspec = nullptr, *d_max = nullptr, *d_in = nullptr, *d_in2 = nullptr,
-         *d_out = nullptr;
-    size_t num_bytes = 0, den_bytes = 0, nspec_bytes = 0, dspec_bytes = 0, max_bytes = 0, in_bytes = 0, in2_bytes = 0, out_bytes = 0;
+    PlanHandle fft;  // one frame of n samples per row (create_row_fft)
+    DevBuf d_num, d_den, d_nspec, d_dspec, d_max, d_in, d_in2, d_out;
     mutable std::string err;
 };
 
 namespace {
-
-thread_local std::string g_fir_err, g_deconv_err;
-
-template <typename P>
-std::string &create_err();
-template <> std::string &create_err<sgx_fir>() { return g_fir_err; }
-template <> std::string &create_err<sgx_deconv>() { return g_deconv_err; }
-
-template <typename P>
-sgx_status ffail(const P *p, sgx_status st, const std::string &m) {
-    if (p) p->err = m; else create_err<P>() = m;
-    return st;
-}
-#define FIR_HIP(plan, call)                                                                                             \
-    do {                                                                                                                \
-        hipError_t e_ = (call);                                                                                         \
-        if (e_ != hipSuccess)                                                                                           \
-            return ffail(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-const char *const kNoDevice = "hip -- FFT backend error: plan has no HIP device (host-only plan)";
-
-template <typename P>
-sgx_status fgrow(P *p, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) FIR_HIP(p, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    FIR_HIP(p, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
-
-sgx_status upload(sgx_fir *p, void **dst, const std::vector<double> &v) {
-    const size_t bytes = v.size() * p->elem;
-    FIR_HIP(p, hipMalloc(dst, bytes));
-    if (p->dtype == SGX_F64) {
-        FIR_HIP(p, hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> f(v.begin(), v.end());
-        FIR_HIP(p, hipMemcpy(*dst, f.data(), bytes, hipMemcpyHostToDevice));
-    }
-    return SGX_OK;
-}
 
 // The fused route's segment length: next_power_of_two(4 taps) within 256 .. 4096 (taps - 1 <= P / 2 holds for every taps <= 2049)
 size_t fused_len(size_t taps) { return std::min<size_t>(4096, std::max<size_t>(256, next_pow2(4 * taps))); }
@@ -444,9 +395,9 @@ size_t seqs_of(const sgx_fir *p, size_t n_out) { return (n_out + p->S - 1) / p->
 sgx_status gen_reserve(sgx_fir *p, size_t total_seqs) {
     const size_t gc = gen_chunk(p, total_seqs), bytes = gc * p->P * 2 * p->elem;
     sgx_status st;
-    if ((st = fgrow(p, &p->d_seq, &p->seq_bytes, bytes)) != SGX_OK) return st;
-    if ((st = fgrow(p, &p->d_spec, &p->spec_bytes, bytes)) != SGX_OK) return st;
-    if (p->big.M && (st = fgrow(p, &p->d_big, &p->big_bytes, big_scratch_bytes(p->big, p->dtype, gc))) != SGX_OK) return st;
+    if ((st = grow(p, p->d_seq, bytes)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_spec, bytes)) != SGX_OK) return st;
+    if (p->big.M && (st = grow(p, p->d_big, big_scratch_bytes(p->big, p->dtype, gc))) != SGX_OK) return st;
     return SGX_OK;
 }
 
@@ -483,19 +434,19 @@ sgx_status run_generic(sgx_fir *p, const FirArgs &a, hipStream_t s) {
         g.seq = p->d_seq;
         if (f64) hipLaunchKernelGGL(k_fir_gather<double>, dim3(grid), dim3(256), 0, s, g);
         else hipLaunchKernelGGL(k_fir_gather<float>, dim3(grid), dim3(256), 0, s, g);
-        FIR_HIP(p, hipGetLastError());
-        FIR_HIP(p, transform(p->d_seq, p->d_spec, 0, fuse_mul));
+        SGX_TRY_HIP(p, hipGetLastError());
+        SGX_TRY_HIP(p, transform(p->d_seq, p->d_spec, 0, fuse_mul));
         if (!fuse_mul) {
             g.seq = p->d_spec;
             if (f64) hipLaunchKernelGGL(k_fir_mul<double>, dim3(grid), dim3(256), 0, s, g);
             else hipLaunchKernelGGL(k_fir_mul<float>, dim3(grid), dim3(256), 0, s, g);
-            FIR_HIP(p, hipGetLastError());
+            SGX_TRY_HIP(p, hipGetLastError());
         }
-        FIR_HIP(p, transform(p->d_spec, p->d_seq, 1, false));
+        SGX_TRY_HIP(p, transform(p->d_spec, p->d_seq, 1, false));
         g.seq = p->d_seq;
         if (f64) hipLaunchKernelGGL(k_fir_scatter<double>, dim3(grid), dim3(256), 0, s, g);
         else hipLaunchKernelGGL(k_fir_scatter<float>, dim3(grid), dim3(256), 0, s, g);
-        FIR_HIP(p, hipGetLastError());
+        SGX_TRY_HIP(p, hipGetLastError());
     }
     return SGX_OK;
 }
@@ -503,16 +454,10 @@ sgx_status run_generic(sgx_fir *p, const FirArgs &a, hipStream_t s) {
 // the history buffers for `rows` rows; new buffers start as zeros (a call that grows them follows creation or reset)
 sgx_status hist_reserve(sgx_fir *p, size_t rows, hipStream_t s) {
     const size_t need = rows * (p->taps - 1) * p->elem;
-    if (need == 0 || p->hist_bytes >= need) return SGX_OK;
-    for (void *&h : p->d_hist) {
-        if (h) FIR_HIP(p, hipFree(h));
-        h = nullptr;
-    }
-    p->hist_bytes = 0;
-    FIR_HIP(p, hipMalloc(&p->d_hist[0], need));
-    FIR_HIP(p, hipMalloc(&p->d_hist[1], need));
-    p->hist_bytes = need;
-    FIR_HIP(p, hipMemsetAsync(p->d_hist[0], 0, need, s));
+    if (need == 0 || p->d_hist[1].bytes >= need) return SGX_OK;  // ([1] grows last: both are there)
+    sgx_status st;
+    if ((st = grow(p, p->d_hist[0], need)) != SGX_OK || (st = grow(p, p->d_hist[1], need)) != SGX_OK) return st;
+    SGX_TRY_HIP(p, hipMemsetAsync(p->d_hist[0], 0, need, s));
     return SGX_OK;
 }
 
@@ -521,14 +466,14 @@ sgx_status run_dev(sgx_fir *p, const void *x, size_t batch, size_t n_samples, si
     const size_t L = p->taps - 1;
     FirArgs a{};
     a.x = x; a.out = out;
-    a.hist = streaming && L ? p->d_hist[0] : nullptr;
+    a.hist = streaming && L ? p->d_hist[0].ptr : nullptr;
     a.H = p->d_H; a.tw = p->d_tw;
     a.sample_stride = stride; a.n_samples = n_samples; a.n_out = n_out;
     a.h_stride = p->ir_rows > 1 ? p->P : 0;
     a.batch = unsigned(batch); a.L = unsigned(L); a.S = unsigned(p->S);
     a.nseq = unsigned(seqs_of(p, n_out));
     if (p->fused) {
-        FIR_HIP(p, launch_os(p, a, s));
+        SGX_TRY_HIP(p, launch_os(p, a, s));
     } else {
         const sgx_status st = run_generic(p, a, s);
         if (st != SGX_OK) return st;
@@ -536,52 +481,50 @@ sgx_status run_dev(sgx_fir *p, const void *x, size_t batch, size_t n_samples, si
     if (streaming && L) {
         const unsigned grid = grid_for(batch * L);
         if (p->dtype == SGX_F64)
-            hipLaunchKernelGGL(k_fir_hist<double>, dim3(grid), dim3(256), 0, s, (const double *)x, stride, n_samples, (const double *)p->d_hist[0],
-                               (double *)p->d_hist[1], unsigned(L), unsigned(batch));
+            hipLaunchKernelGGL(k_fir_hist<double>, dim3(grid), dim3(256), 0, s, (const double *)x, stride, n_samples, p->d_hist[0].as<double>(),
+                               p->d_hist[1].as<double>(), unsigned(L), unsigned(batch));
         else
-            hipLaunchKernelGGL(k_fir_hist<float>, dim3(grid), dim3(256), 0, s, (const float *)x, stride, n_samples, (const float *)p->d_hist[0],
-                               (float *)p->d_hist[1], unsigned(L), unsigned(batch));
-        FIR_HIP(p, hipGetLastError());
-        FIR_HIP(p, hipMemcpyAsync(p->d_hist[0], p->d_hist[1], batch * L * p->elem, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL(k_fir_hist<float>, dim3(grid), dim3(256), 0, s, (const float *)x, stride, n_samples, p->d_hist[0].as<float>(),
+                               p->d_hist[1].as<float>(), unsigned(L), unsigned(batch));
+        SGX_TRY_HIP(p, hipGetLastError());
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_hist[0], p->d_hist[1], batch * L * p->elem, hipMemcpyDeviceToDevice, s));
     }
     return SGX_OK;
 }
 
 sgx_status fir_call(sgx_fir *p, const void *x, size_t batch, size_t n_samples, size_t stride, void *out, size_t out_elems, int32_t mem_kind,
                     void *stream, bool streaming) {
-    if (!p) return ffail<sgx_fir>(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!x || !out) return ffail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || n_samples == 0) return ffail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
-    if (stride < n_samples) return ffail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!x || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || n_samples == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
+    if (stride < n_samples) return fail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
     if (p->ir_rows > 1 && batch != p->ir_rows)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(p->ir_rows) + ", got " + std::to_string(batch) +
-                                              " (the plan holds one impulse response per row)");
+        return dim_mismatch(p, p->ir_rows, batch, " (the plan holds one impulse response per row)");
     if (streaming && p->rows && batch != p->rows)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(p->rows) + ", got " + std::to_string(batch) +
-                                              " (rows of the history; reset() releases them)");
+        return dim_mismatch(p, p->rows, batch, " (rows of the history; reset() releases them)");
     const size_t n_out = streaming ? n_samples : n_samples + p->taps - 1;
     if (out_elems != batch * n_out)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(batch * n_out) + ", got " + std::to_string(out_elems));
+        return dim_mismatch(p, batch * n_out, out_elems);
     const size_t nseq = seqs_of(p, n_out);
     if (batch > 0xffffffffull || nseq * batch >= 0x7fffffffull || n_samples > (size_t(1) << 40))
-        return ffail(p, SGX_INVALID_INPUT, "Invalid input: batch or sample count too large");
-    if (p->device == -2) return ffail(p, SGX_BACKEND, kNoDevice);
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return ffail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+        return fail(p, SGX_INVALID_INPUT, "Invalid input: batch or sample count too large");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard dg;
-    FIR_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     sgx_status st;
     if (streaming && (st = hist_reserve(p, batch, s)) != SGX_OK) return st;
     if (mem_kind == SGX_MEM_DEVICE) {
         st = run_dev(p, x, batch, n_samples, stride, out, n_out, streaming, s);
     } else {
         const size_t in_bytes = ((batch - 1) * stride + n_samples) * p->elem, out_bytes = out_elems * p->elem;
-        if ((st = fgrow(p, &p->d_in, &p->in_bytes, in_bytes)) != SGX_OK) return st;
-        if ((st = fgrow(p, &p->d_out, &p->out_bytes, out_bytes)) != SGX_OK) return st;
-        FIR_HIP(p, hipMemcpyAsync(p->d_in, x, in_bytes, hipMemcpyHostToDevice, s));
+        if ((st = grow(p, p->d_in, in_bytes)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, out_bytes)) != SGX_OK) return st;
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in, x, in_bytes, hipMemcpyHostToDevice, s));
         if ((st = run_dev(p, p->d_in, batch, n_samples, stride, p->d_out, n_out, streaming, s)) != SGX_OK) return st;
-        FIR_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-        FIR_HIP(p, hipStreamSynchronize(s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        SGX_TRY_HIP(p, hipStreamSynchronize(s));
     }
     if (st == SGX_OK && streaming) p->rows = batch;
     return st;
@@ -594,20 +537,20 @@ extern "C" {
 sgx_status sgx_fir_create(const double *ir, size_t taps, size_t ir_rows, size_t block_size, int32_t route, int32_t dtype, int32_t device,
                           sgx_fir **out) {
     if (out) *out = nullptr;
-    auto bad = [&](const std::string &m) { return ffail<sgx_fir>(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
+    auto bad = [&](const std::string &m) { return fail<sgx_fir>(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
     if (!out) return bad("null argument");
     if (taps == 0 || !ir) return bad("impulse response must not be empty");  // src/convolution.rs:172-176
     if (ir_rows == 0) return bad("ir_rows must be > 0");
     if (dtype != SGX_F32 && dtype != SGX_F64) return bad("dtype must be f32 or f64");
     if (route != SGX_FIR_ROUTE_AUTO && route != SGX_FIR_ROUTE_GENERIC) return bad("unknown route");
     if (taps > kMaxTaps)
-        return ffail<sgx_fir>(nullptr, SGX_BACKEND, "hip -- FFT backend error: an impulse response of " + std::to_string(taps) +
+        return fail<sgx_fir>(nullptr, SGX_BACKEND, "hip -- FFT backend error: an impulse response of " + std::to_string(taps) +
                                                          " taps is not supported (up to 524288)");
     if (ir_rows > 0xffffffffull || ir_rows * generic_len(taps) > (size_t(1) << 28)) return bad("too many impulse responses of this length");
     sgx_fir *p = new (std::nothrow) sgx_fir();
-    if (!p) return ffail<sgx_fir>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
+    if (!p) return fail<sgx_fir>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->taps = taps; p->ir_rows = ir_rows; p->block = block_size;
-    p->dtype = dtype; p->elem = esize(dtype); p->device = device;
+    p->dtype = dtype; p->elem = elem_size(dtype); p->device = device;
     p->fused = route == SGX_FIR_ROUTE_AUTO && taps <= kMaxFusedTaps;
     p->P = p->fused ? fused_len(taps) : generic_len(taps);
     p->S = p->P - (taps - 1);
@@ -618,9 +561,9 @@ sgx_status sgx_fir_create(const double *ir, size_t taps, size_t ir_rows, size_t 
     if (device == -2) { *out = p; return SGX_OK; }  // host-only: validation, shapes, route
 
     auto tables = [&]() -> sgx_status {
-        if (device == -1) FIR_HIP(p, hipGetDevice(&p->device));
+        if (device == -1) SGX_TRY_HIP(p, hipGetDevice(&p->device));
         DeviceGuard dg;
-        FIR_HIP(p, dg.enter(p->device));
+        SGX_TRY_HIP(p, dg.enter(p->device));
         const size_t P = p->P;
         // H = FFT_P(h) / P in f64, rounded to T: the fused route in bs_middle's product order ([k3][k1][k2] for bin k1 + A (k2 + B k3),
         // [k2][k1] for the two-pass splits), the generic route in natural order
@@ -641,7 +584,7 @@ sgx_status sgx_fir_create(const double *ir, size_t taps, size_t ir_rows, size_t 
             }
         }
         sgx_status st;
-        if ((st = upload(p, &p->d_H, H)) != SGX_OK) return st;
+        if ((st = upload(p, p->d_H, H, dtype)) != SGX_OK) return st;
         if (P <= 4096) {
             std::vector<double> tw(2 * P);
             for (size_t k = 0; k < P; ++k) {
@@ -649,35 +592,23 @@ sgx_status sgx_fir_create(const double *ir, size_t taps, size_t ir_rows, size_t 
                 tw[2 * k] = std::cos(a);
                 tw[2 * k + 1] = std::sin(a);
             }
-            if ((st = upload(p, &p->d_tw, tw)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_tw, tw, dtype)) != SGX_OK) return st;
         } else {
             BigHost h;
             if (!big_host_tables(unsigned(P), h))
-                return ffail(p, SGX_BACKEND, "hip -- FFT backend error: no complex transform for length " + std::to_string(P));
-            FIR_HIP(p, big_upload(h, dtype, p->big));
+                return fail(p, SGX_BACKEND, "hip -- FFT backend error: no complex transform for length " + std::to_string(P));
+            SGX_TRY_HIP(p, big_upload(h, dtype, p->big));
         }
         return SGX_OK;
     };
-    const sgx_status st = tables();
-    if (st != SGX_OK) {
-        g_fir_err = p->err;
-        sgx_fir_destroy(p);
-        return st;
-    }
-    *out = p;
-    return SGX_OK;
+    return finish_create(p, tables(), out, sgx_fir_destroy);
 }
 
 void sgx_fir_destroy(sgx_fir *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        if (p->big.M) big_free(p->big);
-        void *bufs[] = {p->d_H, p->d_tw, p->d_big, p->d_seq, p->d_spec, p->d_in, p->d_out, p->d_hist[0], p->d_hist[1]};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-    }
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
+    big_free(p->big);
     delete p;
 }
 
@@ -692,31 +623,30 @@ sgx_status sgx_fir_convolve(sgx_fir *p, const void *x, size_t batch, size_t n_sa
 }
 
 sgx_status sgx_fir_reset(sgx_fir *p, void *stream) {
-    if (!p) return ffail<sgx_fir>(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
     p->rows = 0;
-    if (p->device == -2 || !p->d_hist[0]) return SGX_OK;
+    if (p->device == -2 || !p->d_hist[0].ptr) return SGX_OK;
     DeviceGuard dg;
-    FIR_HIP(p, dg.enter(p->device));
-    FIR_HIP(p, hipMemsetAsync(p->d_hist[0], 0, p->hist_bytes, static_cast<hipStream_t>(stream)));
+    SGX_TRY_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, hipMemsetAsync(p->d_hist[0], 0, p->d_hist[0].bytes, static_cast<hipStream_t>(stream)));
     return SGX_OK;
 }
 
 sgx_status sgx_fir_reserve(sgx_fir *p, size_t batch, size_t n_samples, int32_t host_staging) {
-    if (!p || batch == 0 || n_samples == 0) return ffail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
-    if (p->device == -2) return ffail(p, SGX_BACKEND, kNoDevice);
+    if (!p || batch == 0 || n_samples == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     if (p->rows && batch > p->rows)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(p->rows) + ", got " + std::to_string(batch) +
-                                              " (rows of the history; reset() releases them)");
+        return dim_mismatch(p, p->rows, batch, " (rows of the history; reset() releases them)");
     DeviceGuard dg;
-    FIR_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     sgx_status st;
     if ((st = hist_reserve(p, batch, nullptr)) != SGX_OK) return st;
-    FIR_HIP(p, hipStreamSynchronize(nullptr));
+    SGX_TRY_HIP(p, hipStreamSynchronize(nullptr));
     const size_t n_full = n_samples + p->taps - 1;
     if (!p->fused && (st = gen_reserve(p, batch * seqs_of(p, n_full))) != SGX_OK) return st;
     if (host_staging) {
-        if ((st = fgrow(p, &p->d_in, &p->in_bytes, batch * n_samples * p->elem)) != SGX_OK) return st;
-        if ((st = fgrow(p, &p->d_out, &p->out_bytes, batch * n_full * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in, batch * n_samples * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, batch * n_full * p->elem)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
@@ -726,52 +656,39 @@ size_t sgx_fir_step(const sgx_fir *p) { return p ? p->S : 0; }
 size_t sgx_fir_taps(const sgx_fir *p) { return p ? p->taps : 0; }
 const char *sgx_fir_kernel_name(const sgx_fir *p) { return !p ? "" : p->fused ? "k_fir_os" : "fir_generic"; }
 int32_t sgx_fir_device(const sgx_fir *p) { return p ? p->device : -2; }
-const char *sgx_fir_last_error(const sgx_fir *p) { return p ? p->err.c_str() : g_fir_err.c_str(); }
+const char *sgx_fir_last_error(const sgx_fir *p) { return p ? p->err.c_str() : create_err<sgx_fir>().c_str(); }
 
 // ---- deconvolution ---------------------------------------------------------------------------------------------------------------
 sgx_status sgx_deconv_create(size_t n_len, size_t d_len, double regularization, int32_t dtype, int32_t device, sgx_deconv **out) {
     if (out) *out = nullptr;
-    auto bad = [&](const std::string &m) { return ffail<sgx_deconv>(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
+    auto bad = [&](const std::string &m) { return fail<sgx_deconv>(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
     if (!out) return bad("null argument");
     if (n_len == 0 || d_len == 0) return bad("numerator and denominator must not be empty");  // NonEmptySlice
     if (dtype != SGX_F32 && dtype != SGX_F64) return bad("dtype must be f32 or f64");
     if (!std::isfinite(regularization)) return bad("regularization must be finite");
     const size_t n = next_pow2(std::max(n_len, d_len));
     if (n > (size_t(1) << 20))
-        return ffail<sgx_deconv>(nullptr, SGX_BACKEND, "hip -- FFT backend error: a transform of " + std::to_string(n) +
+        return fail<sgx_deconv>(nullptr, SGX_BACKEND, "hip -- FFT backend error: a transform of " + std::to_string(n) +
                                                             " points is not supported (up to 1048576)");
     sgx_deconv *p = new (std::nothrow) sgx_deconv();
-    if (!p) return ffail<sgx_deconv>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
+    if (!p) return fail<sgx_deconv>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->n_len = n_len; p->d_len = d_len; p->n = n; p->nb = n / 2 + 1;
     p->out_len = std::max<size_t>(1, n_len >= d_len ? n_len - d_len + 1 : n_len);
-    p->reg = regularization; p->dtype = dtype; p->elem = esize(dtype); p->device = device;
-    sgx_params sp{};
-    sp.n_fft = uint32_t(n); sp.hop_size = uint32_t(n); sp.centre = 0;
-    sp.window_kind = SGX_WIN_RECTANGULAR;
-    sp.sample_rate_hz = 1.0;
-    sp.freq_scale = SGX_FREQ_LINEAR; sp.amp_scale = SGX_AMP_COMPLEX;
-    sp.dtype = dtype; sp.device = device;
-    const sgx_status st = sgx_plan_create(&sp, &p->fft);
+    p->reg = regularization; p->dtype = dtype; p->elem = elem_size(dtype); p->device = device;
+    const sgx_status st = create_row_fft(n, dtype, device, p->fft);
     if (st != SGX_OK) {
-        g_deconv_err = sgx_last_create_error();
         delete p;
-        return st;
+        return fail<sgx_deconv>(nullptr, st, sgx_last_create_error());
     }
-    p->device = sgx_plan_device(p->fft);
+    p->device = sgx_plan_device(p->fft.get());
     *out = p;
     return SGX_OK;
 }
 
 void sgx_deconv_destroy(sgx_deconv *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        void *bufs[] = {p->d_num, p->d_den, p->d_nspec, p->d_dspec, p->d_max, p->d_in, p->d_in2, p->d_out};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-    }
-    if (p->fft) sgx_plan_destroy(p->fft);
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
     delete p;
 }
 
@@ -779,49 +696,50 @@ size_t sgx_deconv_output_length(const sgx_deconv *p) { return p ? p->out_len : 0
 
 sgx_status sgx_deconv_reserve(sgx_deconv *p, size_t batch, size_t den_rows, int32_t host_staging) {
     if (!p || batch == 0 || (den_rows != 1 && den_rows != batch))
-        return ffail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0 and den_rows 1 or batch");
-    if (p->device == -2) return ffail(p, SGX_BACKEND, kNoDevice);
+        return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0 and den_rows 1 or batch");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    FIR_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
+    sgx_plan *fft = p->fft.get();
     sgx_status st;
-    if ((st = fgrow(p, &p->d_num, &p->num_bytes, batch * p->n * p->elem)) != SGX_OK) return st;
-    if ((st = fgrow(p, &p->d_den, &p->den_bytes, den_rows * p->n * p->elem)) != SGX_OK) return st;
-    if ((st = fgrow(p, &p->d_nspec, &p->nspec_bytes, batch * p->nb * 2 * p->elem)) != SGX_OK) return st;
-    if ((st = fgrow(p, &p->d_dspec, &p->dspec_bytes, den_rows * p->nb * 2 * p->elem)) != SGX_OK) return st;
-    if ((st = fgrow(p, &p->d_max, &p->max_bytes, den_rows * p->elem)) != SGX_OK) return st;
-    if (sgx_reserve(p->fft, batch, p->n, 0, 0) != SGX_OK || sgx_reserve(p->fft, batch, p->n, 0, 1) != SGX_OK)
-        return ffail(p, SGX_BACKEND, sgx_last_error(p->fft));
+    if ((st = grow(p, p->d_num, batch * p->n * p->elem)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_den, den_rows * p->n * p->elem)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_nspec, batch * p->nb * 2 * p->elem)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_dspec, den_rows * p->nb * 2 * p->elem)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_max, den_rows * p->elem)) != SGX_OK) return st;
+    if (sgx_reserve(fft, batch, p->n, 0, 0) != SGX_OK || sgx_reserve(fft, batch, p->n, 0, 1) != SGX_OK)
+        return fail(p, SGX_BACKEND, sgx_last_error(fft));
     if (host_staging) {
-        if ((st = fgrow(p, &p->d_in, &p->in_bytes, batch * p->n_len * p->elem)) != SGX_OK) return st;
-        if ((st = fgrow(p, &p->d_in2, &p->in2_bytes, den_rows * p->d_len * p->elem)) != SGX_OK) return st;
-        if ((st = fgrow(p, &p->d_out, &p->out_bytes, batch * p->out_len * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in, batch * p->n_len * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in2, den_rows * p->d_len * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, batch * p->out_len * p->elem)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
 
 sgx_status sgx_deconv_execute(sgx_deconv *p, const void *numerator, const void *denominator, size_t batch, size_t den_rows, void *out,
                               size_t out_elems, int32_t mem_kind, void *stream) {
-    if (!p) return ffail<sgx_deconv>(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!numerator || !denominator || !out) return ffail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || batch > 65535) return ffail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!numerator || !denominator || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || batch > 65535) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
     if (den_rows != 1 && den_rows != batch)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(batch) + ", got " + std::to_string(den_rows) +
-                                              " (denominator rows: 1 or one per numerator row)");
+        return dim_mismatch(p, batch, den_rows, " (denominator rows: 1 or one per numerator row)");
     if (out_elems != batch * p->out_len)
-        return ffail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(batch * p->out_len) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return ffail(p, SGX_BACKEND, kNoDevice);
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return ffail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+        return dim_mismatch(p, batch * p->out_len, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard dg;
-    FIR_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     sgx_status st = sgx_deconv_reserve(p, batch, den_rows, mem_kind == SGX_MEM_HOST);
     if (st != SGX_OK) return st;
     const size_t es = p->elem, n = p->n, nb = p->nb;
+    sgx_plan *fft = p->fft.get();
     const void *num = numerator, *den = denominator;
     void *dst = out;
     if (mem_kind == SGX_MEM_HOST) {
-        FIR_HIP(p, hipMemcpyAsync(p->d_in, numerator, batch * p->n_len * es, hipMemcpyHostToDevice, s));
-        FIR_HIP(p, hipMemcpyAsync(p->d_in2, denominator, den_rows * p->d_len * es, hipMemcpyHostToDevice, s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in, numerator, batch * p->n_len * es, hipMemcpyHostToDevice, s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in2, denominator, den_rows * p->d_len * es, hipMemcpyHostToDevice, s));
         num = p->d_in; den = p->d_in2; dst = p->d_out;
     }
     auto rows = [&](const void *in, void *to, size_t nrows, size_t w_in, size_t w_out) {
@@ -830,33 +748,33 @@ sgx_status sgx_deconv_execute(sgx_deconv *p, const void *numerator, const void *
         return hipGetLastError();
     };
     // rows zero-padded to n
-    FIR_HIP(p, rows(num, p->d_num, batch, p->n_len, n));
-    FIR_HIP(p, rows(den, p->d_den, den_rows, p->d_len, n));
-    auto fft_fail = [&]() { return ffail(p, SGX_BACKEND, sgx_last_error(p->fft)); };
-    if (sgx_execute(p->fft, p->d_num, batch, n, n, p->d_nspec, batch * nb * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
-    if (sgx_execute(p->fft, p->d_den, den_rows, n, n, p->d_dspec, den_rows * nb * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    SGX_TRY_HIP(p, rows(num, p->d_num, batch, p->n_len, n));
+    SGX_TRY_HIP(p, rows(den, p->d_den, den_rows, p->d_len, n));
+    auto fft_fail = [&]() { return fail(p, SGX_BACKEND, sgx_last_error(fft)); };
+    if (sgx_execute(fft, p->d_num, batch, n, n, p->d_nspec, batch * nb * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    if (sgx_execute(fft, p->d_den, den_rows, n, n, p->d_dspec, den_rows * nb * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
     const unsigned long long total = (unsigned long long)batch * nb, d_stride = den_rows > 1 ? nb : 0;
     if (p->dtype == SGX_F64) {
-        hipLaunchKernelGGL(k_deconv_max<double>, dim3(unsigned(den_rows)), dim3(256), 0, s, (const inreg::v2d *)p->d_dspec, unsigned(nb), (double *)p->d_max);
-        hipLaunchKernelGGL(k_deconv_quot<double>, dim3(grid_for(total)), dim3(256), 0, s, (inreg::v2d *)p->d_nspec, (const inreg::v2d *)p->d_dspec,
-                           (const double *)p->d_max, unsigned(nb), unsigned(n), total, d_stride, p->reg);
+        hipLaunchKernelGGL(k_deconv_max<double>, dim3(unsigned(den_rows)), dim3(256), 0, s, p->d_dspec.as<inreg::v2d>(), unsigned(nb), p->d_max.as<double>());
+        hipLaunchKernelGGL(k_deconv_quot<double>, dim3(grid_for(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2d>(), p->d_dspec.as<inreg::v2d>(),
+                           p->d_max.as<double>(), unsigned(nb), unsigned(n), total, d_stride, p->reg);
     } else {
-        hipLaunchKernelGGL(k_deconv_max<float>, dim3(unsigned(den_rows)), dim3(256), 0, s, (const inreg::v2f *)p->d_dspec, unsigned(nb), (float *)p->d_max);
-        hipLaunchKernelGGL(k_deconv_quot<float>, dim3(grid_for(total)), dim3(256), 0, s, (inreg::v2f *)p->d_nspec, (const inreg::v2f *)p->d_dspec,
-                           (const float *)p->d_max, unsigned(nb), unsigned(n), total, d_stride, float(p->reg));
+        hipLaunchKernelGGL(k_deconv_max<float>, dim3(unsigned(den_rows)), dim3(256), 0, s, p->d_dspec.as<inreg::v2f>(), unsigned(nb), p->d_max.as<float>());
+        hipLaunchKernelGGL(k_deconv_quot<float>, dim3(grid_for(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2f>(), p->d_dspec.as<inreg::v2f>(),
+                           p->d_max.as<float>(), unsigned(nb), unsigned(n), total, d_stride, float(p->reg));
     }
-    FIR_HIP(p, hipGetLastError());
+    SGX_TRY_HIP(p, hipGetLastError());
     // y = irfft_n(Q) over the padded numerator rows (no longer needed), then the first out_len samples of each row
-    if (sgx_istft(p->fft, p->d_nspec, batch, nb, 1, p->d_num, batch * n, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
-    FIR_HIP(p, rows(p->d_num, dst, batch, n, p->out_len));
+    if (sgx_istft(fft, p->d_nspec, batch, nb, 1, p->d_num, batch * n, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    SGX_TRY_HIP(p, rows(p->d_num, dst, batch, n, p->out_len));
     if (mem_kind == SGX_MEM_HOST) {
-        FIR_HIP(p, hipMemcpyAsync(out, p->d_out, batch * p->out_len * es, hipMemcpyDeviceToHost, s));
-        FIR_HIP(p, hipStreamSynchronize(s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, batch * p->out_len * es, hipMemcpyDeviceToHost, s));
+        SGX_TRY_HIP(p, hipStreamSynchronize(s));
     }
     return SGX_OK;
 }
 
 int32_t sgx_deconv_device(const sgx_deconv *p) { return p ? p->device : -2; }
-const char *sgx_deconv_last_error(const sgx_deconv *p) { return p ? p->err.c_str() : g_deconv_err.c_str(); }
+const char *sgx_deconv_last_error(const sgx_deconv *p) { return p ? p->err.c_str() : create_err<sgx_deconv>().c_str(); }
 
 }  // extern "C"

@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "db_f64.h"
-#include "sgx_internal.h"
+#include "plan_host.h"
 
 using namespace sgx;
 
@@ -115,8 +115,6 @@ __global__ __launch_bounds__(kGtLanes) void k_gammatone_iir(GtArgs a) {
     ((T *)a.out)[((size_t)b * a.n_bands + band) * a.n_frames + f] = v;
 }
 
-size_t esize(int dtype) { return dtype == SGX_F64 ? 8 : 4; }
-
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------------
@@ -128,35 +126,11 @@ struct sgx_gammatone {
     bool db = false;
     double eps = 0.0, floor_val = 0.0;
     std::vector<double> centres, coef, window;  // coef [n_bands][kCoef]
-    void *d_win = nullptr, *d_coef = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t in_bytes = 0, out_bytes = 0;
+    DevBuf d_win, d_coef, d_in, d_out;
     mutable std::string err;
 };
 
 namespace {
-
-thread_local std::string g_gt_err;
-
-sgx_status gfail(const sgx_gammatone *p, sgx_status st, const std::string &m) {
-    if (p) p->err = m; else g_gt_err = m;
-    return st;
-}
-#define GT_HIP(plan, call)                                                                                            \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess)                                                                                         \
-            return gfail(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-sgx_status ggrow(sgx_gammatone *p, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) GT_HIP(p, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    GT_HIP(p, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
 
 // iir_gain (src/erb.rs:426-453) from the centre frequency: complex values as (re, im) pairs with num_complex's formulas (product,
 // powi(4) by squaring, quotient by the squared norm, hypot).  Evaluated in long double and rounded once: for low bands x5 loses its leading
@@ -227,12 +201,12 @@ size_t frames_of(const sgx_gammatone *p, size_t n_samples) { return 1 + (n_sampl
 sgx_status run_dev(sgx_gammatone *p, const void *in, size_t batch, size_t stride, size_t n_frames, void *out, hipStream_t s) {
     GtArgs a{};
     a.x = in; a.out = out;
-    a.win = (const double *)p->d_win; a.coef = (const double *)p->d_coef;
+    a.win = p->d_win.as<double>(); a.coef = p->d_coef.as<double>();
     a.sample_stride = stride;
     a.pairs = (unsigned long long)n_frames * p->n_bands;
     a.frame = unsigned(p->frame); a.hop = unsigned(p->hop); a.n_frames = unsigned(n_frames); a.n_bands = unsigned(p->n_bands);
     const unsigned long long wgs = (a.pairs + kGtLanes - 1) / kGtLanes;
-    if (wgs * batch >= 0x7fffffffull) return gfail(p, SGX_INVALID_INPUT, "Invalid input: batch x frames x bands too large for one launch");
+    if (wgs * batch >= 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch x frames x bands too large for one launch");
     a.wgs = unsigned(wgs);
     // frames a workgroup's 256 consecutive pairs can touch, and the chunk of each that fits kGtLds beside the others'
     // (a workgroup starts at a multiple of 256, i.e. of g = gcd(256, n_bands), so at most n_bands - g pairs into a frame)
@@ -249,7 +223,7 @@ sgx_status run_dev(sgx_gammatone *p, const void *in, size_t batch, size_t stride
     const dim3 grid(unsigned(wgs * batch));
     if (p->dtype == SGX_F64) hipLaunchKernelGGL(k_gammatone_iir<double>, grid, dim3(kGtLanes), lds, s, a);
     else hipLaunchKernelGGL(k_gammatone_iir<float>, grid, dim3(kGtLanes), lds, s, a);
-    GT_HIP(p, hipGetLastError());
+    SGX_TRY_HIP(p, hipGetLastError());
     return SGX_OK;
 }
 
@@ -261,8 +235,8 @@ sgx_status sgx_gammatone_create(double sample_rate, size_t frame_size, size_t ho
                                 int32_t erb_spacing, int32_t has_db_floor, double db_floor, int32_t dtype, int32_t device,
                                 sgx_gammatone **out) {
     if (out) *out = nullptr;
-    if (!out) return gfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
-    auto bad = [&](const char *m) { return gfail(nullptr, SGX_INVALID_INPUT, std::string("Invalid input: ") + m); };
+    if (!out) return fail<sgx_gammatone>(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
+    auto bad = [&](const char *m) { return fail<sgx_gammatone>(nullptr, SGX_INVALID_INPUT, std::string("Invalid input: ") + m); };
     if (sample_rate <= 0.0) return bad("sample_rate must be > 0");  // src/erb.rs:610-612
     if (!std::isfinite(sample_rate)) return bad("sample_rate must be finite");
     if (frame_size < 2) return bad("frame_size must be >= 2");  // the window divides by frame_size - 1
@@ -278,9 +252,9 @@ sgx_status sgx_gammatone_create(double sample_rate, size_t frame_size, size_t ho
     if (has_db_floor && !std::isfinite(db_floor)) return bad("db_floor must be finite");
     if (dtype != SGX_F32 && dtype != SGX_F64) return bad("dtype must be f32 or f64");
     sgx_gammatone *p = new (std::nothrow) sgx_gammatone();
-    if (!p) return gfail(nullptr, SGX_INTERNAL, "Internal error: out of memory");
+    if (!p) return fail<sgx_gammatone>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->sample_rate = sample_rate; p->frame = frame_size; p->hop = hop_size; p->n_bands = n_filters;
-    p->dtype = dtype; p->elem = esize(dtype); p->device = device;
+    p->dtype = dtype; p->elem = elem_size(dtype); p->device = device;
     erb_center_freqs(n_filters, f_min, f_max, erb_spacing, p->centres);
     build_bank(p->centres, sample_rate, p->coef);
     p->window.resize(frame_size);  // hann_window :545-549 (the divisor is frame_size - 1)
@@ -300,39 +274,25 @@ sgx_status sgx_gammatone_create(double sample_rate, size_t frame_size, size_t ho
     if (device == -2) { *out = p; return SGX_OK; }  // host-only: validation, shapes, centre frequencies, coefficients, route
 
     auto tables = [&]() -> sgx_status {
-        if (device == -1) GT_HIP(p, hipGetDevice(&p->device));
+        if (device == -1) SGX_TRY_HIP(p, hipGetDevice(&p->device));
         DeviceGuard dg;
-        GT_HIP(p, dg.enter(p->device));
-        GT_HIP(p, hipMalloc(&p->d_win, p->window.size() * sizeof(double)));
-        GT_HIP(p, hipMemcpy(p->d_win, p->window.data(), p->window.size() * sizeof(double), hipMemcpyHostToDevice));
-        GT_HIP(p, hipMalloc(&p->d_coef, p->coef.size() * sizeof(double)));
-        GT_HIP(p, hipMemcpy(p->d_coef, p->coef.data(), p->coef.size() * sizeof(double), hipMemcpyHostToDevice));
-        return SGX_OK;
+        SGX_TRY_HIP(p, dg.enter(p->device));
+        const sgx_status st = upload(p, p->d_win, p->window, SGX_F64);  // the recurrences run in f64 for both types
+        return st != SGX_OK ? st : upload(p, p->d_coef, p->coef, SGX_F64);
     };
-    const sgx_status st = tables();
-    if (st != SGX_OK) {
-        g_gt_err = p->err;
-        sgx_gammatone_destroy(p);
-        return st;
-    }
-    *out = p;
-    return SGX_OK;
+    return finish_create(p, tables(), out, sgx_gammatone_destroy);
 }
 
 void sgx_gammatone_destroy(sgx_gammatone *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        for (void *b : {p->d_win, p->d_coef, p->d_in, p->d_out})
-            if (b) (void)hipFree(b);
-    }
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
     delete p;
 }
 
 sgx_status sgx_gammatone_output_shape(const sgx_gammatone *p, size_t n_samples, size_t *n_bands, size_t *n_frames) {
-    if (!p || !n_bands || !n_frames) return gfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
-    if (n_samples < p->frame) return gfail(p, SGX_INVALID_INPUT, "Invalid input: signal is shorter than frame_size");  // src/erb.rs:616-620
+    if (!p || !n_bands || !n_frames) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (n_samples < p->frame) return fail(p, SGX_INVALID_INPUT, "Invalid input: signal is shorter than frame_size");  // src/erb.rs:616-620
     *n_bands = p->n_bands;
     *n_frames = frames_of(p, n_samples);
     return SGX_OK;
@@ -340,63 +300,63 @@ sgx_status sgx_gammatone_output_shape(const sgx_gammatone *p, size_t n_samples, 
 
 sgx_status sgx_gammatone_execute(sgx_gammatone *p, const void *samples, size_t batch, size_t n_samples, size_t sample_stride, void *out,
                                  size_t out_elems, int32_t mem_kind, void *hip_stream) {
-    if (!p) return gfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!samples || !out) return gfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0) return gfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!samples || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
     size_t nb, nf;
     sgx_status st = sgx_gammatone_output_shape(p, n_samples, &nb, &nf);
     if (st != SGX_OK) return st;
-    if (sample_stride < n_samples) return gfail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride must be >= n_samples");
-    if (batch > 0x7fffffffull || nf > 0x7fffffffull) return gfail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
+    if (sample_stride < n_samples) return fail(p, SGX_INVALID_INPUT, "Invalid input: sample_stride must be >= n_samples");
+    if (batch > 0x7fffffffull || nf > 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
     const size_t expected = batch * nb * nf;
     if (out_elems != expected)
-        return gfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return gfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return dim_mismatch(p, expected, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard dg;
-    GT_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     if (mem_kind == SGX_MEM_DEVICE) return run_dev(p, samples, batch, sample_stride, nf, out, s);
-    if (mem_kind != SGX_MEM_HOST) return gfail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+    if (mem_kind != SGX_MEM_HOST) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     // host rows are staged densely (row stride n_samples on the device)
     const size_t row_bytes = n_samples * p->elem, out_bytes = expected * p->elem;
-    if ((st = ggrow(p, &p->d_in, &p->in_bytes, batch * row_bytes)) != SGX_OK) return st;
-    if ((st = ggrow(p, &p->d_out, &p->out_bytes, out_bytes)) != SGX_OK) return st;
-    GT_HIP(p, hipMemcpy2DAsync(p->d_in, row_bytes, samples, sample_stride * p->elem, row_bytes, batch, hipMemcpyHostToDevice, s));
+    if ((st = grow(p, p->d_in, batch * row_bytes)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_out, out_bytes)) != SGX_OK) return st;
+    SGX_TRY_HIP(p, hipMemcpy2DAsync(p->d_in, row_bytes, samples, sample_stride * p->elem, row_bytes, batch, hipMemcpyHostToDevice, s));
     if ((st = run_dev(p, p->d_in, batch, n_samples, nf, p->d_out, s)) != SGX_OK) return st;
-    GT_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    GT_HIP(p, hipStreamSynchronize(s));
+    SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(p, hipStreamSynchronize(s));
     return SGX_OK;
 }
 
 sgx_status sgx_gammatone_center_frequencies(const sgx_gammatone *p, double *out) {
-    if (!p || !out) return gfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     std::memcpy(out, p->centres.data(), p->centres.size() * sizeof(double));
     return SGX_OK;
 }
 
 sgx_status sgx_gammatone_coefficients(const sgx_gammatone *p, double *out) {
-    if (!p || !out) return gfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     std::memcpy(out, p->coef.data(), p->coef.size() * sizeof(double));
     return SGX_OK;
 }
 
 sgx_status sgx_gammatone_reserve(sgx_gammatone *p, size_t batch, size_t n_samples, int32_t host_staging) {
-    if (!p || batch == 0) return gfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
-    if (p->device == -2) return gfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+    if (!p || batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     size_t nb, nf;
     sgx_status st = sgx_gammatone_output_shape(p, n_samples, &nb, &nf);
     if (st != SGX_OK) return st;
     if (!host_staging) return SGX_OK;
     DeviceGuard dg;
-    GT_HIP(p, dg.enter(p->device));
-    if ((st = ggrow(p, &p->d_in, &p->in_bytes, batch * n_samples * p->elem)) != SGX_OK) return st;
-    return ggrow(p, &p->d_out, &p->out_bytes, batch * nb * nf * p->elem);
+    SGX_TRY_HIP(p, dg.enter(p->device));
+    if ((st = grow(p, p->d_in, batch * n_samples * p->elem)) != SGX_OK) return st;
+    return grow(p, p->d_out, batch * nb * nf * p->elem);
 }
 
 const char *sgx_gammatone_kernel_name(const sgx_gammatone *p) { return p ? "k_gammatone_iir" : ""; }
 
 int32_t sgx_gammatone_device(const sgx_gammatone *p) { return p ? p->device : -2; }
 
-const char *sgx_gammatone_last_error(const sgx_gammatone *p) { return p ? p->err.c_str() : g_gt_err.c_str(); }
+const char *sgx_gammatone_last_error(const sgx_gammatone *p) { return p ? p->err.c_str() : create_err<sgx_gammatone>().c_str(); }
 
 }  // extern "C"

@@ -40,7 +40,7 @@
 
 #include "reg_radix.h"
 #include "rr_layout.h"
-#include "sgx_internal.h"
+#include "plan_host.h"
 #include "xcd_map.h"
 
 using namespace sgx;
@@ -51,7 +51,6 @@ constexpr double kPiM = 3.14159265358979323846264338327950288;
 constexpr size_t kMdctLds = 72 * 1024;           // LDS per workgroup of the fused kernels: two workgroups per CU
 constexpr size_t kChunkBytes = size_t(256) << 20;  // generic route: scratch per buffer; a call is cut into chunks of frames
 constexpr size_t kMaxWindow = 8192, kMaxWindowPow2 = 16384;
-
 
 struct MdctArgs {
     const void *in;   // forward: samples [batch][n_samples]; inverse: coefficients [batch][N][n_frames]
@@ -266,12 +265,10 @@ hipError_t launch_fused_t(const MdctArgs &a, bool inverse, unsigned ltile, size_
     return hipGetLastError();
 }
 
-size_t esize(int dtype) { return dtype == SGX_F64 ? 8 : 4; }
-
 // LDS bytes of one frame of the fused kernels' tile, 0 if M has no pass split
 size_t fused_frame_bytes(unsigned M, int dtype, unsigned *fa, unsigned *fb, unsigned *fc) {
     if (!reg_split_len(M, dtype, fa, fb, fc)) return 0;
-    const size_t es = esize(dtype);
+    const size_t es = elem_size(dtype);
     return (size_t)rr_frame_stride(*fa, rr_swizzle(2 * (unsigned)es, *fa, *fb, *fc).rs) * 2 * es;
 }
 
@@ -481,50 +478,14 @@ struct sgx_mdct {
     std::vector<double> custom, window;
     bool fused_fwd = false, fused_inv = false;
     unsigned L = 0;  // generic route: transform length
-    void *d_win = nullptr, *d_t1 = nullptr, *d_t2 = nullptr, *d_t2i = nullptr, *d_tw = nullptr;  // fused and generic (N even)
-    void *d_pa = nullptr, *d_pb = nullptr, *d_phi = nullptr, *d_psi = nullptr, *d_twL = nullptr;  // generic, N odd (twL: W_L, L = N)
+    DevBuf d_win, d_t1, d_t2, d_t2i, d_tw;       // fused and generic (N even)
+    DevBuf d_pa, d_pb, d_phi, d_psi, d_twL;      // generic, N odd (twL: W_L, L = N)
     BsDevTables bs;
-    void *d_seq = nullptr, *d_spec = nullptr, *d_frames = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t seq_bytes = 0, spec_bytes = 0, frames_bytes = 0, in_bytes = 0, out_bytes = 0;
+    DevBuf d_seq, d_spec, d_frames, d_in, d_out;
     mutable std::string err;
 };
 
 namespace {
-
-thread_local std::string g_mdct_err;
-
-sgx_status mfail(const sgx_mdct *p, sgx_status st, const std::string &m) {
-    if (p) p->err = m; else g_mdct_err = m;
-    return st;
-}
-#define MD_HIP(plan, call)                                                                                            \
-    do {                                                                                                              \
-        hipError_t e_ = (call);                                                                                       \
-        if (e_ != hipSuccess)                                                                                         \
-            return mfail(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-sgx_status mgrow(sgx_mdct *p, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) MD_HIP(p, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    MD_HIP(p, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
-
-sgx_status upload(sgx_mdct *p, void **dst, const std::vector<double> &v) {
-    const size_t bytes = v.size() * p->elem;
-    MD_HIP(p, hipMalloc(dst, bytes));
-    if (p->dtype == SGX_F64) {
-        MD_HIP(p, hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> f(v.begin(), v.end());
-        MD_HIP(p, hipMemcpy(*dst, f.data(), bytes, hipMemcpyHostToDevice));
-    }
-    return SGX_OK;
-}
 
 // e^(i ang(k)) for k < n, interleaved, times `scale`
 template <typename F>
@@ -555,9 +516,9 @@ GenSizes gen_sizes(const sgx_mdct *p, size_t total_frames, bool inverse) {
 sgx_status gen_reserve(sgx_mdct *p, size_t total_frames, bool inverse) {
     const GenSizes z = gen_sizes(p, total_frames, inverse);
     sgx_status st;
-    if ((st = mgrow(p, &p->d_seq, &p->seq_bytes, z.seq)) != SGX_OK) return st;
-    if (p->L >= 16 && (st = mgrow(p, &p->d_spec, &p->spec_bytes, z.seq)) != SGX_OK) return st;
-    if (inverse && (st = mgrow(p, &p->d_frames, &p->frames_bytes, z.frames)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_seq, z.seq)) != SGX_OK) return st;
+    if (p->L >= 16 && (st = grow(p, p->d_spec, z.seq)) != SGX_OK) return st;
+    if (inverse && (st = grow(p, p->d_frames, z.frames)) != SGX_OK) return st;
     return SGX_OK;
 }
 
@@ -576,7 +537,7 @@ sgx_status run_generic(sgx_mdct *p, const void *in, size_t batch, size_t n_sampl
     a.spec = a.direct ? p->d_seq : p->d_spec;
     a.n_samples = n_samples; a.out_len = inv_len(p, n_frames);
     a.N = unsigned(p->n); a.hop = unsigned(p->hop); a.n_frames = unsigned(n_frames); a.L = p->L;
-    if (inverse) MD_HIP(p, hipMemsetAsync(out, 0, batch * a.out_len * p->elem, s));
+    if (inverse) SGX_TRY_HIP(p, hipMemsetAsync(out, 0, batch * a.out_len * p->elem, s));
     const bool f64 = p->dtype == SGX_F64;
     for (size_t g0 = 0; g0 < total; g0 += z.gc) {
         a.g0 = g0;
@@ -585,7 +546,7 @@ sgx_status run_generic(sgx_mdct *p, const void *in, size_t batch, size_t n_sampl
         const unsigned long long fold_total = nseq * p->L;
         if (f64) hipLaunchKernelGGL(k_mdct_fold<double>, dim3(grid_for(fold_total)), dim3(256), 0, s, a, int(inverse));
         else hipLaunchKernelGGL(k_mdct_fold<float>, dim3(grid_for(fold_total)), dim3(256), 0, s, a, int(inverse));
-        MD_HIP(p, hipGetLastError());
+        SGX_TRY_HIP(p, hipGetLastError());
         if (!a.direct) {
             C2cArgs c{};
             c.in = p->d_seq; c.out = p->d_spec;
@@ -601,17 +562,17 @@ sgx_status run_generic(sgx_mdct *p, const void *in, size_t batch, size_t n_sampl
             hipError_t e = launch_c2c_reg(c, p->dtype, s);
             if (e == hipErrorNotSupported && p->bs.M) e = launch_c2c_bluestein(c, p->bs, p->dtype, s);
             if (e == hipErrorNotSupported) e = launch_c2c_tile(c, p->dtype, s);
-            MD_HIP(p, e);
+            SGX_TRY_HIP(p, e);
         }
         const unsigned long long post_total = a.gc * (inverse ? 2ull * p->n : p->n);
         if (f64) hipLaunchKernelGGL(k_mdct_post<double>, dim3(grid_for(post_total)), dim3(256), 0, s, a, int(inverse));
         else hipLaunchKernelGGL(k_mdct_post<float>, dim3(grid_for(post_total)), dim3(256), 0, s, a, int(inverse));
-        MD_HIP(p, hipGetLastError());
+        SGX_TRY_HIP(p, hipGetLastError());
         if (inverse) {
             const unsigned long long b0 = g0 / n_frames, b1 = (g0 + a.gc - 1) / n_frames, nsig = b1 - b0 + 1;
             if (f64) hipLaunchKernelGGL(k_mdct_ola<double>, dim3(grid_for(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
             else hipLaunchKernelGGL(k_mdct_ola<float>, dim3(grid_for(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
-            MD_HIP(p, hipGetLastError());
+            SGX_TRY_HIP(p, hipGetLastError());
         }
     }
     return SGX_OK;
@@ -625,7 +586,7 @@ sgx_status run_dev(sgx_mdct *p, const void *in, size_t batch, size_t n_samples, 
         a.batch = unsigned(batch); a.hop = unsigned(p->hop); a.n_frames = unsigned(n_frames);
         const hipError_t e = launch_fused(a, unsigned(p->n / 2), p->dtype, inverse, s);
         if (e != hipErrorNotSupported) {
-            MD_HIP(p, e);
+            SGX_TRY_HIP(p, e);
             return SGX_OK;
         }
     }
@@ -665,14 +626,14 @@ extern "C" {
 sgx_status sgx_mdct_create(size_t window_size, size_t hop_size, int32_t window_kind, double window_param, const double *custom_window,
                            uint32_t custom_window_len, int32_t dtype, int32_t device, sgx_mdct **out) {
     if (out) *out = nullptr;
-    if (!out) return mfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!out) return fail<sgx_mdct>(nullptr, SGX_INVALID_INPUT, "Invalid input: null argument");
     std::string msg;
     const sgx_status vs = validate(window_size, hop_size, window_kind, custom_window, custom_window_len, dtype, msg);
-    if (vs != SGX_OK) return mfail(nullptr, vs, msg);
+    if (vs != SGX_OK) return fail<sgx_mdct>(nullptr, vs, msg);
     sgx_mdct *p = new (std::nothrow) sgx_mdct();
-    if (!p) return mfail(nullptr, SGX_INTERNAL, "Internal error: out of memory");
+    if (!p) return fail<sgx_mdct>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->two_n = window_size; p->n = window_size / 2; p->hop = hop_size;
-    p->dtype = dtype; p->elem = esize(dtype); p->device = device;
+    p->dtype = dtype; p->elem = elem_size(dtype); p->device = device;
     p->window_kind = window_kind; p->window_param = window_param;
     if (window_kind == SGX_WIN_CUSTOM) p->custom.assign(custom_window, custom_window + custom_window_len);
     sgx_params wp{};
@@ -692,70 +653,55 @@ sgx_status sgx_mdct_create(size_t window_size, size_t hop_size, int32_t window_k
     if (device == -2) { *out = p; return SGX_OK; }  // host-only: validation, shapes, window, routes
 
     auto tables = [&]() -> sgx_status {
-        if (device == -1) MD_HIP(p, hipGetDevice(&p->device));
+        if (device == -1) SGX_TRY_HIP(p, hipGetDevice(&p->device));
         DeviceGuard dg;
-        MD_HIP(p, dg.enter(p->device));
+        SGX_TRY_HIP(p, dg.enter(p->device));
         sgx_status st;
-        if ((st = upload(p, &p->d_win, p->window)) != SGX_OK) return st;
+        if ((st = upload(p, p->d_win, p->window, dtype)) != SGX_OK) return st;
         const double n = double(N);
         if (N % 2 == 0) {
-            if ((st = upload(p, &p->d_t1, ctab(M, 1.0, [&](double k) { return -kPiM * (4.0 * k + 1.0) / (4.0 * n); }))) != SGX_OK) return st;
-            if ((st = upload(p, &p->d_t2, ctab(M, 1.0, [&](double k) { return -kPiM * k / n; }))) != SGX_OK) return st;
-            if ((st = upload(p, &p->d_t2i, ctab(M, 2.0 / n, [&](double k) { return -kPiM * k / n; }))) != SGX_OK) return st;
-            if ((st = upload(p, &p->d_tw, ctab(M, 1.0, [&](double k) { return -2.0 * kPiM * k / double(M); }))) != SGX_OK) return st;
+            if ((st = upload(p, p->d_t1, ctab(M, 1.0, [&](double k) { return -kPiM * (4.0 * k + 1.0) / (4.0 * n); }), dtype)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_t2, ctab(M, 1.0, [&](double k) { return -kPiM * k / n; }), dtype)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_t2i, ctab(M, 2.0 / n, [&](double k) { return -kPiM * k / n; }), dtype)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_tw, ctab(M, 1.0, [&](double k) { return -2.0 * kPiM * k / double(M); }), dtype)) != SGX_OK) return st;
         } else {
-            if ((st = upload(p, &p->d_pa, ctab(2 * N, 1.0, [&](double k) { return -kPiM * k / (2.0 * n); }))) != SGX_OK) return st;
-            if ((st = upload(p, &p->d_pb, ctab(N, 1.0, [&](double k) { return -kPiM * k / n; }))) != SGX_OK) return st;
+            if ((st = upload(p, p->d_pa, ctab(2 * N, 1.0, [&](double k) { return -kPiM * k / (2.0 * n); }), dtype)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_pb, ctab(N, 1.0, [&](double k) { return -kPiM * k / n; }), dtype)) != SGX_OK) return st;
             // (the product (1 + N)(2k + 1) reduced mod 8N in integers first: the angle itself reaches N pi / 2)
-            if ((st = upload(p, &p->d_phi, ctab(N, 1.0, [&](double k) {
+            if ((st = upload(p, p->d_phi, ctab(N, 1.0, [&](double k) {
                      const unsigned long long r = (unsigned long long)(N + 1) * (2ull * (unsigned long long)k + 1ull) % (8ull * N);
                      return -kPiM * double(r) / (4.0 * n);
-                 }))) != SGX_OK)
+                 }), dtype)) != SGX_OK)
                 return st;
             const double off = double((N + 1) / 2);
-            if ((st = upload(p, &p->d_psi, ctab(2 * N, 2.0 / n, [&](double m) { return -kPiM * (m + off) / (2.0 * n); }))) != SGX_OK) return st;
-            if ((st = upload(p, &p->d_twL, ctab(N, 1.0, [&](double k) { return -2.0 * kPiM * k / n; }))) != SGX_OK) return st;
+            if ((st = upload(p, p->d_psi, ctab(2 * N, 2.0 / n, [&](double m) { return -kPiM * (m + off) / (2.0 * n); }), dtype)) != SGX_OK) return st;
+            if ((st = upload(p, p->d_twL, ctab(N, 1.0, [&](double k) { return -2.0 * kPiM * k / n; }), dtype)) != SGX_OK) return st;
         }
         // generic route: chirp-z tables for a transform length without a pass split (as fft2d.hip's c2c_dispatch)
         const unsigned L = p->L;
         BsHostTables h;
         if (L >= 16 && (L & (L - 1)) != 0 && !reg_split_len(L, dtype, &fa, &fb, &fc) && bluestein_host_tables(L, dtype, h)) {
-            auto up = [&](void **dst, const std::vector<double> &v) { return upload(p, dst, v); };
-            if ((st = up(&p->bs.chirp, h.chirp)) != SGX_OK || (st = up(&p->bs.bhp, h.bhp)) != SGX_OK || (st = up(&p->bs.tw, h.tw)) != SGX_OK)
-                return st;
-            p->bs.M = h.M;
+            if ((st = upload_bs(p, p->bs, h, dtype)) != SGX_OK) return st;
         }
         if (L >= 16 && !reg_split_len(L, dtype, &fa, &fb, &fc) && !p->bs.M && fft2d_tile_for(L, dtype) == 0)
-            return mfail(p, SGX_BACKEND, "hip -- FFT backend error: no complex transform kernel for length " + std::to_string(L));
+            return fail(p, SGX_BACKEND, "hip -- FFT backend error: no complex transform kernel for length " + std::to_string(L));
         return SGX_OK;
     };
-    const sgx_status st = tables();
-    if (st != SGX_OK) {
-        g_mdct_err = p->err;
-        sgx_mdct_destroy(p);
-        return st;
-    }
-    *out = p;
-    return SGX_OK;
+    return finish_create(p, tables(), out, sgx_mdct_destroy);
 }
 
 void sgx_mdct_destroy(sgx_mdct *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        void *bufs[] = {p->d_win, p->d_t1, p->d_t2, p->d_t2i, p->d_tw, p->d_pa, p->d_pb, p->d_phi, p->d_psi, p->d_twL,
-                        p->bs.chirp, p->bs.bhp, p->bs.tw, p->d_seq, p->d_spec, p->d_frames, p->d_in, p->d_out};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-    }
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
+    bs_free(p->bs);
     delete p;
 }
 
 sgx_status sgx_mdct_output_shape(const sgx_mdct *p, size_t n_samples, size_t *n_coeffs, size_t *n_frames) {
-    if (!p || !n_coeffs || !n_frames) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !n_coeffs || !n_frames) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     if (n_samples < p->two_n)
-        return mfail(p, SGX_INVALID_INPUT, "Invalid input: samples length (" + std::to_string(n_samples) + ") must be >= window_size (" +
+        return fail(p, SGX_INVALID_INPUT, "Invalid input: samples length (" + std::to_string(n_samples) + ") must be >= window_size (" +
                                                std::to_string(p->two_n) + ")");  // src/mdct.rs:398-404
     *n_coeffs = p->n;
     *n_frames = frames_of(p, n_samples);
@@ -763,24 +709,24 @@ sgx_status sgx_mdct_output_shape(const sgx_mdct *p, size_t n_samples, size_t *n_
 }
 
 sgx_status sgx_mdct_inverse_length(const sgx_mdct *p, size_t n_frames, size_t *n_samples) {
-    if (!p || !n_samples) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !n_samples) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     *n_samples = inv_len(p, n_frames);
     return SGX_OK;
 }
 
 sgx_status sgx_mdct_forward(sgx_mdct *p, const void *samples, size_t batch, size_t n_samples, void *out, size_t out_elems, int32_t mem_kind,
                             void *hip_stream) {
-    if (!p) return mfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!samples || !out) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!samples || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
     size_t nc, nf;
     sgx_status st = sgx_mdct_output_shape(p, n_samples, &nc, &nf);
     if (st != SGX_OK) return st;
-    if (batch > 0xffffffffull || nf > 0x7fffffffull) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
+    if (batch > 0xffffffffull || nf > 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
     const size_t expected = batch * nc * nf;
     if (out_elems != expected)
-        return mfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return mfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return dim_mismatch(p, expected, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return with_staging(p, samples, batch * n_samples * p->elem, out, expected * p->elem, mem_kind, s,
                         [&](const void *i, void *o) { return run_dev(p, i, batch, n_samples, nf, o, false, s); });
@@ -788,44 +734,43 @@ sgx_status sgx_mdct_forward(sgx_mdct *p, const void *samples, size_t batch, size
 
 sgx_status sgx_mdct_inverse(sgx_mdct *p, const void *coeffs, size_t batch, size_t n_coeffs, size_t n_frames, void *out, size_t out_elems,
                             int32_t mem_kind, void *hip_stream) {
-    if (!p) return mfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (batch == 0) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
     if (n_coeffs != p->n)  // src/mdct.rs:451-457
-        return mfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(p->n) + ", got " + std::to_string(n_coeffs) +
-                                              " (coefficients has " + std::to_string(n_coeffs) + " rows but params.n_coefficients() = " +
-                                              std::to_string(p->n) + ")");
-    if (batch > 0xffffffffull || n_frames > 0x7fffffffull) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
+        return dim_mismatch(p, p->n, n_coeffs,
+                            " (coefficients has " + std::to_string(n_coeffs) + " rows but params.n_coefficients() = " + std::to_string(p->n) + ")");
+    if (batch > 0xffffffffull || n_frames > 0x7fffffffull) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
     const size_t len = inv_len(p, n_frames), expected = batch * len;
     if (out_elems != expected)
-        return mfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(out_elems));
+        return dim_mismatch(p, expected, out_elems);
     if (n_frames == 0) return SGX_OK;  // zero frames: an empty output (src/mdct.rs:459-462)
-    if (!coeffs || !out) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (p->device == -2) return mfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+    if (!coeffs || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return with_staging(p, coeffs, batch * n_coeffs * n_frames * p->elem, out, expected * p->elem, mem_kind, s,
                         [&](const void *i, void *o) { return run_dev(p, i, batch, 0, n_frames, o, true, s); });
 }
 
 sgx_status sgx_mdct_reserve(sgx_mdct *p, size_t batch, size_t n_samples, int32_t host_staging) {
-    if (!p || batch == 0) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
-    if (p->device == -2) return mfail(p, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+    if (!p || batch == 0) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be > 0");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     size_t nc, nf;
     sgx_status st = sgx_mdct_output_shape(p, n_samples, &nc, &nf);
     if (st != SGX_OK) return st;
     DeviceGuard dg;
-    MD_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     if (!p->fused_fwd && (st = gen_reserve(p, batch * nf, false)) != SGX_OK) return st;
     if (!p->fused_inv && (st = gen_reserve(p, batch * nf, true)) != SGX_OK) return st;
     if (host_staging) {
         const size_t big = std::max(batch * n_samples, std::max(batch * nc * nf, batch * inv_len(p, nf))) * p->elem;
-        if ((st = mgrow(p, &p->d_in, &p->in_bytes, big)) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_out, &p->out_bytes, big)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in, big)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, big)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
 
 sgx_status sgx_mdct_window(const sgx_mdct *p, double *out) {
-    if (!p || !out) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (!p || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null argument");
     std::memcpy(out, p->window.data(), p->window.size() * sizeof(double));
     return SGX_OK;
 }
@@ -838,7 +783,7 @@ const char *sgx_mdct_kernel_name(const sgx_mdct *p, int32_t inverse) {
 
 int32_t sgx_mdct_device(const sgx_mdct *p) { return p ? p->device : -2; }
 
-const char *sgx_mdct_last_error(const sgx_mdct *p) { return p ? p->err.c_str() : g_mdct_err.c_str(); }
+const char *sgx_mdct_last_error(const sgx_mdct *p) { return p ? p->err.c_str() : create_err<sgx_mdct>().c_str(); }
 
 }  // extern "C"
 
@@ -847,16 +792,16 @@ namespace {
 sgx_status with_staging(sgx_mdct *p, const void *in, size_t in_bytes, void *out, size_t out_bytes, int mem_kind, hipStream_t s,
                         const std::function<sgx_status(const void *, void *)> &body) {
     DeviceGuard dg;
-    MD_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     if (mem_kind == SGX_MEM_DEVICE) return body(in, out);
-    if (mem_kind != SGX_MEM_HOST) return mfail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+    if (mem_kind != SGX_MEM_HOST) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     sgx_status st;
-    if ((st = mgrow(p, &p->d_in, &p->in_bytes, in_bytes)) != SGX_OK) return st;
-    if ((st = mgrow(p, &p->d_out, &p->out_bytes, out_bytes)) != SGX_OK) return st;
-    MD_HIP(p, hipMemcpyAsync(p->d_in, in, in_bytes, hipMemcpyHostToDevice, s));
+    if ((st = grow(p, p->d_in, in_bytes)) != SGX_OK) return st;
+    if ((st = grow(p, p->d_out, out_bytes)) != SGX_OK) return st;
+    SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in, in, in_bytes, hipMemcpyHostToDevice, s));
     if ((st = body(p->d_in, p->d_out)) != SGX_OK) return st;
-    MD_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    MD_HIP(p, hipStreamSynchronize(s));
+    SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(p, hipStreamSynchronize(s));
     return SGX_OK;
 }
 

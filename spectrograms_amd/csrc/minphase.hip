@@ -42,7 +42,7 @@
 #include <string>
 #include <vector>
 
-#include "sgx_internal.h"
+#include "plan_host.h"
 
 using namespace sgx;
 
@@ -390,48 +390,22 @@ struct sgx_minphase {
     int dtype = SGX_F32, device = -1;
     size_t elem = 4;
     bool fused = false;
-    void *d_tw = nullptr, *d_twr = nullptr;  // fused: W_n^k [n / 2] and, in the slot order of the pair steps, [n / 4], complex f64
-    sgx_plan *fft = nullptr;   // generic: f64, one frame of n samples per row (sgx_execute = batched R2C, sgx_istft = batched C2R)
-    void *d_x = nullptr, *d_y = nullptr, *d_spec = nullptr, *d_spec2 = nullptr, *d_max = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t x_bytes = 0, y_bytes = 0, spec_bytes = 0, spec2_bytes = 0, max_bytes = 0, in_bytes = 0, out_bytes = 0;
+    DevBuf d_tw, d_twr;  // fused: W_n^k [n / 2] and, in the slot order of the pair steps, [n / 4], complex f64
+    PlanHandle fft;      // generic: f64, one frame of n samples per row (create_row_fft)
+    DevBuf d_x, d_y, d_spec, d_spec2, d_max, d_in, d_out;
     mutable std::string err;
 };
 
 namespace {
 
-thread_local std::string g_minphase_err;
-
-sgx_status mfail(const sgx_minphase *p, sgx_status st, const std::string &m) {
-    if (p) p->err = m; else g_minphase_err = m;
-    return st;
-}
-#define MP_HIP(plan, call)                                                                                              \
-    do {                                                                                                                \
-        hipError_t e_ = (call);                                                                                         \
-        if (e_ != hipSuccess)                                                                                           \
-            return mfail(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-const char *const kMpNoDevice = "hip -- FFT backend error: plan has no HIP device (host-only plan)";
-
-sgx_status mgrow(sgx_minphase *p, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) MP_HIP(p, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    MP_HIP(p, hipMalloc(buf, need));
-    *have = need;
-    return SGX_OK;
-}
-
 sgx_status run_fused(sgx_minphase *p, const void *ir, size_t batch, void *out, hipStream_t s) {
     MpArgs a{};
-    a.ir = ir; a.out = out; a.tw = (const cd *)p->d_tw; a.twr = (const cd *)p->d_twr;
+    a.ir = ir; a.out = out; a.tw = p->d_tw.as<cd>(); a.twr = p->d_twr.as<cd>();
     a.taps = unsigned(p->taps); a.n = unsigned(p->n); a.out_len = unsigned(p->out_len);
     a.f32 = p->dtype == SGX_F32;
     const size_t lds = std::max<size_t>(1, p->n / 2) * sizeof(cd);  // <= 32 KB
     hipLaunchKernelGGL(k_minphase, dim3(unsigned(batch)), dim3(kMpThreads), lds, s, a);
-    MP_HIP(p, hipGetLastError());
+    SGX_TRY_HIP(p, hipGetLastError());
     return SGX_OK;
 }
 
@@ -440,24 +414,25 @@ sgx_status run_generic(sgx_minphase *p, const void *ir, size_t batch, void *out,
     const unsigned long long samples = (unsigned long long)batch * n, bins = (unsigned long long)batch * nb,
                              outs = (unsigned long long)batch * p->out_len;
     const int f32 = p->dtype == SGX_F32;
-    double *x = (double *)p->d_x, *y = (double *)p->d_y;
-    cd *spec = (cd *)p->d_spec, *spec2 = (cd *)p->d_spec2;
-    auto fft_fail = [&]() { return mfail(p, SGX_BACKEND, sgx_last_error(p->fft)); };
+    double *x = p->d_x.as<double>(), *y = p->d_y.as<double>();
+    cd *spec = p->d_spec.as<cd>(), *spec2 = p->d_spec2.as<cd>();
+    sgx_plan *fft = p->fft.get();
+    auto fft_fail = [&]() { return fail(p, SGX_BACKEND, sgx_last_error(fft)); };
     hipLaunchKernelGGL(k_mp_widen, dim3(mp_grid(samples)), dim3(256), 0, s, ir, x, (unsigned long long)batch, unsigned(p->taps), unsigned(n), f32);
-    MP_HIP(p, hipGetLastError());
-    if (sgx_execute(p->fft, x, batch, n, n, spec, bins * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
-    hipLaunchKernelGGL(k_mp_max, dim3(unsigned(batch)), dim3(256), 0, s, (const cd *)spec, unsigned(nb), (double *)p->d_max);
-    hipLaunchKernelGGL(k_mp_log, dim3(mp_grid(bins)), dim3(256), 0, s, (const cd *)spec, (const double *)p->d_max, spec2, unsigned(nb), bins);
-    MP_HIP(p, hipGetLastError());
-    if (sgx_istft(p->fft, spec2, batch, nb, 1, y, samples, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    SGX_TRY_HIP(p, hipGetLastError());
+    if (sgx_execute(fft, x, batch, n, n, spec, bins * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    hipLaunchKernelGGL(k_mp_max, dim3(unsigned(batch)), dim3(256), 0, s, (const cd *)spec, unsigned(nb), p->d_max.as<double>());
+    hipLaunchKernelGGL(k_mp_log, dim3(mp_grid(bins)), dim3(256), 0, s, (const cd *)spec, p->d_max.as<double>(), spec2, unsigned(nb), bins);
+    SGX_TRY_HIP(p, hipGetLastError());
+    if (sgx_istft(fft, spec2, batch, nb, 1, y, samples, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
     hipLaunchKernelGGL(k_mp_fold, dim3(mp_grid(samples)), dim3(256), 0, s, (const double *)y, x, unsigned(n), samples);
-    MP_HIP(p, hipGetLastError());
-    if (sgx_execute(p->fft, x, batch, n, n, spec, bins * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    SGX_TRY_HIP(p, hipGetLastError());
+    if (sgx_execute(fft, x, batch, n, n, spec, bins * 2, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
     hipLaunchKernelGGL(k_mp_exp, dim3(mp_grid(bins)), dim3(256), 0, s, (const cd *)spec, spec2, unsigned(nb), unsigned(n), bins);
-    MP_HIP(p, hipGetLastError());
-    if (sgx_istft(p->fft, spec2, batch, nb, 1, y, samples, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
+    SGX_TRY_HIP(p, hipGetLastError());
+    if (sgx_istft(fft, spec2, batch, nb, 1, y, samples, SGX_MEM_DEVICE, s) != SGX_OK) return fft_fail();
     hipLaunchKernelGGL(k_mp_out, dim3(mp_grid(outs)), dim3(256), 0, s, (const double *)y, out, unsigned(n), unsigned(p->out_len), outs, f32);
-    MP_HIP(p, hipGetLastError());
+    SGX_TRY_HIP(p, hipGetLastError());
     return SGX_OK;
 }
 
@@ -467,7 +442,7 @@ extern "C" {
 
 sgx_status sgx_minphase_create(size_t taps, size_t out_len, size_t oversample, int32_t route, int32_t dtype, int32_t device, sgx_minphase **out) {
     if (out) *out = nullptr;
-    auto bad = [&](const std::string &m) { return mfail(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
+    auto bad = [&](const std::string &m) { return fail<sgx_minphase>(nullptr, SGX_INVALID_INPUT, "Invalid input: " + m); };
     if (!out) return bad("null argument");
     if (taps == 0) return bad("impulse response must not be empty");   // src/min_phase.rs:72-76
     if (out_len == 0) return bad("out_len must be greater than zero");  // :77-81
@@ -481,28 +456,28 @@ sgx_status sgx_minphase_create(size_t taps, size_t out_len, size_t oversample, i
         if (n > kMaxN) n = 0;
     }
     if (n == 0)
-        return mfail(nullptr, SGX_BACKEND, "hip -- FFT backend error: a transform of next_power_of_two(" + std::to_string(taps) + " x " +
+        return fail<sgx_minphase>(nullptr, SGX_BACKEND, "hip -- FFT backend error: a transform of next_power_of_two(" + std::to_string(taps) + " x " +
                                                std::to_string(os) + ") points is not supported (up to 1048576)");
     sgx_minphase *p = new (std::nothrow) sgx_minphase();
-    if (!p) return mfail(nullptr, SGX_INTERNAL, "Internal error: out of memory");
+    if (!p) return fail<sgx_minphase>(nullptr, SGX_INTERNAL, "Internal error: out of memory");
     p->taps = taps; p->n = n; p->nb = n / 2 + 1; p->out_len = std::min(out_len, n);
-    p->dtype = dtype; p->elem = dtype == SGX_F64 ? 8 : 4; p->device = device;
+    p->dtype = dtype; p->elem = elem_size(dtype); p->device = device;
     p->fused = route == SGX_MINPHASE_ROUTE_AUTO && n <= kMaxFusedN;
     if (device == -2) { *out = p; return SGX_OK; }  // host-only: validation, shapes, route
 
     auto tables = [&]() -> sgx_status {
         if (p->fused) {
-            if (device == -1) MP_HIP(p, hipGetDevice(&p->device));
+            if (device == -1) SGX_TRY_HIP(p, hipGetDevice(&p->device));
             DeviceGuard dg;
-            MP_HIP(p, dg.enter(p->device));
+            SGX_TRY_HIP(p, dg.enter(p->device));
             std::vector<double> tw(2 * std::max<size_t>(1, n / 2));
             for (size_t k = 0; k < tw.size() / 2; ++k) {
                 const double a = -2.0 * kPiM * double(k) / double(n);
                 tw[2 * k] = std::cos(a);
                 tw[2 * k + 1] = std::sin(a);
             }
-            MP_HIP(p, hipMalloc(&p->d_tw, tw.size() * sizeof(double)));
-            MP_HIP(p, hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+            sgx_status st;
+            if ((st = upload(p, p->d_tw, tw, SGX_F64)) != SGX_OK) return st;
             const unsigned M = unsigned(n / 2);
             unsigned lm = 0;
             while ((1u << lm) < M) ++lm;
@@ -512,90 +487,69 @@ sgx_status sgx_minphase_create(size_t taps, size_t out_len, size_t oversample, i
                 twr[2 * u] = tw[2 * k];
                 twr[2 * u + 1] = tw[2 * k + 1];
             }
-            MP_HIP(p, hipMalloc(&p->d_twr, twr.size() * sizeof(double)));
-            MP_HIP(p, hipMemcpy(p->d_twr, twr.data(), twr.size() * sizeof(double), hipMemcpyHostToDevice));
-            return SGX_OK;
+            return upload(p, p->d_twr, twr, SGX_F64);
         }
-        sgx_params sp{};
-        sp.n_fft = uint32_t(n); sp.hop_size = uint32_t(n); sp.centre = 0;
-        sp.window_kind = SGX_WIN_RECTANGULAR;
-        sp.sample_rate_hz = 1.0;
-        sp.freq_scale = SGX_FREQ_LINEAR; sp.amp_scale = SGX_AMP_COMPLEX;
-        sp.dtype = SGX_F64; sp.device = device;
-        const sgx_status st = sgx_plan_create(&sp, &p->fft);
-        if (st != SGX_OK) return mfail(p, st, sgx_last_create_error());
-        p->device = sgx_plan_device(p->fft);
+        const sgx_status st = create_row_fft(n, SGX_F64, device, p->fft);
+        if (st != SGX_OK) return fail(p, st, sgx_last_create_error());
+        p->device = sgx_plan_device(p->fft.get());
         return SGX_OK;
     };
-    const sgx_status st = tables();
-    if (st != SGX_OK) {
-        g_minphase_err = p->err;
-        sgx_minphase_destroy(p);
-        return st;
-    }
-    *out = p;
-    return SGX_OK;
+    return finish_create(p, tables(), out, sgx_minphase_destroy);
 }
 
 void sgx_minphase_destroy(sgx_minphase *p) {
     if (!p) return;
-    if (p->device != -2) {
-        DeviceGuard dg;
-        (void)dg.enter(p->device);
-        void *bufs[] = {p->d_tw, p->d_twr, p->d_x, p->d_y, p->d_spec, p->d_spec2, p->d_max, p->d_in, p->d_out};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-    }
-    if (p->fft) sgx_plan_destroy(p->fft);
+    DeviceGuard dg;
+    if (p->device != -2) (void)dg.enter(p->device);
     delete p;
 }
 
 sgx_status sgx_minphase_reserve(sgx_minphase *p, size_t batch, int32_t host_staging) {
-    if (!p || batch == 0 || batch > 65535) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
-    if (p->device == -2) return mfail(p, SGX_BACKEND, kMpNoDevice);
+    if (!p || batch == 0 || batch > 65535) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    MP_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     sgx_status st;
     if (!p->fused) {
-        if ((st = mgrow(p, &p->d_x, &p->x_bytes, batch * p->n * sizeof(double))) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_y, &p->y_bytes, batch * p->n * sizeof(double))) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_spec, &p->spec_bytes, batch * p->nb * sizeof(cd))) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_spec2, &p->spec2_bytes, batch * p->nb * sizeof(cd))) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_max, &p->max_bytes, batch * sizeof(double))) != SGX_OK) return st;
-        if (sgx_reserve(p->fft, batch, p->n, 0, 0) != SGX_OK || sgx_reserve(p->fft, batch, p->n, 0, 1) != SGX_OK)
-            return mfail(p, SGX_BACKEND, sgx_last_error(p->fft));
+        if ((st = grow(p, p->d_x, batch * p->n * sizeof(double))) != SGX_OK) return st;
+        if ((st = grow(p, p->d_y, batch * p->n * sizeof(double))) != SGX_OK) return st;
+        if ((st = grow(p, p->d_spec, batch * p->nb * sizeof(cd))) != SGX_OK) return st;
+        if ((st = grow(p, p->d_spec2, batch * p->nb * sizeof(cd))) != SGX_OK) return st;
+        if ((st = grow(p, p->d_max, batch * sizeof(double))) != SGX_OK) return st;
+        if (sgx_reserve(p->fft.get(), batch, p->n, 0, 0) != SGX_OK || sgx_reserve(p->fft.get(), batch, p->n, 0, 1) != SGX_OK)
+            return fail(p, SGX_BACKEND, sgx_last_error(p->fft.get()));
     }
     if (host_staging) {
-        if ((st = mgrow(p, &p->d_in, &p->in_bytes, batch * p->taps * p->elem)) != SGX_OK) return st;
-        if ((st = mgrow(p, &p->d_out, &p->out_bytes, batch * p->out_len * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_in, batch * p->taps * p->elem)) != SGX_OK) return st;
+        if ((st = grow(p, p->d_out, batch * p->out_len * p->elem)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
 
 sgx_status sgx_minphase_execute(sgx_minphase *p, const void *ir, size_t batch, void *out, size_t out_elems, int32_t mem_kind, void *stream) {
-    if (!p) return mfail(nullptr, SGX_INVALID_INPUT, "Invalid input: null plan");
-    if (!ir || !out) return mfail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || batch > 65535) return mfail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
+    if (!p) return fail(p, SGX_INVALID_INPUT, "Invalid input: null plan");
+    if (!ir || !out) return fail(p, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || batch > 65535) return fail(p, SGX_INVALID_INPUT, "Invalid input: batch must be 1 .. 65535");
     if (out_elems != batch * p->out_len)
-        return mfail(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(batch * p->out_len) + ", got " + std::to_string(out_elems));
-    if (p->device == -2) return mfail(p, SGX_BACKEND, kMpNoDevice);
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return mfail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+        return dim_mismatch(p, batch * p->out_len, out_elems);
+    if (p->device == -2) return fail(p, SGX_BACKEND, kNoDeviceText);
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(p, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard dg;
-    MP_HIP(p, dg.enter(p->device));
+    SGX_TRY_HIP(p, dg.enter(p->device));
     sgx_status st = sgx_minphase_reserve(p, batch, mem_kind == SGX_MEM_HOST);
     if (st != SGX_OK) return st;
     const void *src = ir;
     void *dst = out;
     if (mem_kind == SGX_MEM_HOST) {
-        MP_HIP(p, hipMemcpyAsync(p->d_in, ir, batch * p->taps * p->elem, hipMemcpyHostToDevice, s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_in, ir, batch * p->taps * p->elem, hipMemcpyHostToDevice, s));
         src = p->d_in; dst = p->d_out;
     }
     st = p->fused ? run_fused(p, src, batch, dst, s) : run_generic(p, src, batch, dst, s);
     if (st != SGX_OK) return st;
     if (mem_kind == SGX_MEM_HOST) {
-        MP_HIP(p, hipMemcpyAsync(out, p->d_out, batch * p->out_len * p->elem, hipMemcpyDeviceToHost, s));
-        MP_HIP(p, hipStreamSynchronize(s));
+        SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, batch * p->out_len * p->elem, hipMemcpyDeviceToHost, s));
+        SGX_TRY_HIP(p, hipStreamSynchronize(s));
     }
     return SGX_OK;
 }
@@ -605,6 +559,6 @@ size_t sgx_minphase_output_length(const sgx_minphase *p) { return p ? p->out_len
 size_t sgx_minphase_taps(const sgx_minphase *p) { return p ? p->taps : 0; }
 const char *sgx_minphase_kernel_name(const sgx_minphase *p) { return !p ? "" : p->fused ? "k_minphase" : "minphase_generic"; }
 int32_t sgx_minphase_device(const sgx_minphase *p) { return p ? p->device : -2; }
-const char *sgx_minphase_last_error(const sgx_minphase *p) { return p ? p->err.c_str() : g_minphase_err.c_str(); }
+const char *sgx_minphase_last_error(const sgx_minphase *p) { return p ? p->err.c_str() : create_err<sgx_minphase>().c_str(); }
 
 }  // extern "C"

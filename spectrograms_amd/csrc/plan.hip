@@ -14,7 +14,7 @@
 #include "d32x16_layout.h"
 #include "r32x16_layout.h"
 #include "reg_radix.h"
-#include "sgx_internal.h"
+#include "plan_host.h"
 
 // chirp-z vs the direct / two-factor sums: multiply-adds per sample the latter may cost, per log2(M) M / n.  Measured crossovers
 // (64 x 10 s, hop n / 4, profiles/bench_r03_chirpz_crossover.txt): per-bin outputs win from n_fft 17-18 on (0.25); filterbank outputs
@@ -40,33 +40,14 @@ constexpr unsigned kBigMin = 2048;  // frame lengths above this never run an O(n
 #endif
 namespace {
 
-thread_local std::string g_create_err;
 thread_local const char *t_bank_stage = "", *t_bank_epilogue = "";  // filterbank stage of the call in flight: sgx::note_bank_stage below, read by run_device
 
 constexpr double kPi = 3.14159265358979323846264338327950288;
 
-sgx_status set_err(const sgx_plan *p, sgx_status st, const std::string &msg) {
-    if (p) p->err = msg;
+sgx_status create_fail(sgx_status st, const std::string &msg) {  // a create refused before there is a plan: sgx_last_create_error()
+    create_err<sgx_plan>() = msg;
     return st;
 }
-
-sgx_status dim_err(const sgx_plan *p, size_t expected, size_t got) {  // DimensionMismatch{expected, got} (src/error.rs:19-21)
-    if (p) { p->dm_expected = expected; p->dm_got = got; }
-    return set_err(p, SGX_DIM_MISMATCH, "Dimension mismatch: expected " + std::to_string(expected) + ", got " + std::to_string(got));
-}
-
-sgx_status create_fail(sgx_status st, const std::string &msg) {
-    g_create_err = msg;
-    return st;
-}
-
-#define SGX_HIP(plan, call)                                                                        \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_err(plan, SGX_BACKEND, std::string("hip -- FFT backend error: ") + #call +  \
-                                                  ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 // ---- window coefficients (make_window, src/spectrogram.rs:2159-2235), f64 ------------------------
 double i0_polynomial(double x) {  // modified_bessel_i0 :2237-2259 — the reference's A&S polynomial, incl. its
@@ -430,37 +411,10 @@ void build_cqt_kernels(const sgx_params &p, const sgx_cqt_params &c, std::vector
 }
 
 template <typename T>
-sgx_status upload(sgx_plan *pl, void **dst, const std::vector<T> &src) {
+sgx_status upload_raw(sgx_plan *pl, void **dst, const std::vector<T> &src) {  // a table as built; f64 tables that take the plan's type: upload
     if (src.empty()) { *dst = nullptr; return SGX_OK; }
-    SGX_HIP(pl, hipMalloc(dst, src.size() * sizeof(T)));
-    SGX_HIP(pl, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SGX_OK;
-}
-
-template <typename T>
-sgx_status upload_cast(sgx_plan *pl, void **dst, const std::vector<double> &src) {
-    std::vector<T> tmp(src.size());
-    for (size_t i = 0; i < src.size(); ++i) tmp[i] = T(src[i]);  // T::from_f64
-    return upload<T>(pl, dst, tmp);
-}
-
-template <typename T>
-sgx_status upload_bs(sgx_plan *pl, BsDevTables &d, const BsHostTables &h) {  // chirp-z tables of bluestein_host_tables
-    sgx_status st;
-    if ((st = upload_cast<T>(pl, &d.chirp, h.chirp)) != SGX_OK) return st;
-    if ((st = upload_cast<T>(pl, &d.bhp, h.bhp)) != SGX_OK) return st;
-    if ((st = upload_cast<T>(pl, &d.tw, h.tw)) != SGX_OK) return st;
-    d.M = h.M;
-    return SGX_OK;
-}
-
-sgx_status grow(sgx_plan *pl, void **buf, size_t *have, size_t need) {
-    if (*have >= need) return SGX_OK;
-    if (*buf) SGX_HIP(pl, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    SGX_HIP(pl, hipMalloc(buf, need));
-    *have = need;
+    SGX_TRY_HIP(pl, hipMalloc(dst, src.size() * sizeof(T)));
+    SGX_TRY_HIP(pl, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return SGX_OK;
 }
 
@@ -507,7 +461,7 @@ sgx_status cqt_device_tables(sgx_plan *pl) {
         info[4 * g + 1] = lg[g];
         info[4 * g + 2] = 8 * g;
         rows += lg[g];
-        if (rows > (size_t(1) << 31) / 16) return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: CQT kernel tables too large");
+        if (rows > (size_t(1) << 31) / 16) return fail(pl, SGX_BACKEND, "hip -- FFT backend error: CQT kernel tables too large");
     }
     std::vector<T> tab(rows * 16, T(0));
     for (unsigned k = 0; k < nb; ++k) {
@@ -535,9 +489,9 @@ sgx_status cqt_device_tables(sgx_plan *pl) {
     }
     wb[kCqtWaves] = pos;
     sgx_status st;
-    if ((st = upload<T>(pl, &pl->d_cqt_tab, tab)) != SGX_OK) return st;
-    if ((st = upload<uint32_t>(pl, &pl->d_cqt_info, info)) != SGX_OK) return st;
-    return upload<uint32_t>(pl, &pl->d_cqt_len, pl->cqt_len);
+    if ((st = upload_raw<T>(pl, &pl->d_cqt_tab, tab)) != SGX_OK) return st;
+    if ((st = upload_raw<uint32_t>(pl, &pl->d_cqt_info, info)) != SGX_OK) return st;
+    return upload_raw<uint32_t>(pl, &pl->d_cqt_len, pl->cqt_len);
 }
 
 // The shape-specific kernels at the head of the chain, one entry each: all the host code knows about them.  Plan creation starts
@@ -601,7 +555,7 @@ template <typename T>
 sgx_status tuned_tables(sgx_plan *pl, const TunedKernel &k) {
     const unsigned n = pl->p.n_fft, N = k.tw1_rows * k.tw1_cols;
     sgx_status st;
-    if ((st = upload<T>(pl, &pl->d_tw1, twiddle_grid<T>(k.tw1_rows, k.tw1_cols))) != SGX_OK) return st;
+    if ((st = upload_raw<T>(pl, &pl->d_tw1, twiddle_grid<T>(k.tw1_rows, k.tw1_cols))) != SGX_OK) return st;
     std::vector<T> t2;
     if (k.tw2 == TW2_LANES) {
         t2.resize(2 * size_t(k.tw2_rows) * k.tw2_cols);
@@ -622,12 +576,12 @@ sgx_status tuned_tables(sgx_plan *pl, const TunedKernel &k) {
                 q[0] = w[1]; q[1] = -w[0]; q[2] = w[0]; q[3] = w[1];
             }
     }
-    if ((st = upload<T>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
+    if ((st = upload_raw<T>(pl, &pl->d_tw2, t2)) != SGX_OK) return st;
     const unsigned reps = k.window_len ? k.window_len / n : 1u;
     std::vector<T> wh(size_t(n) * reps), oh(size_t(n) * reps, T(0.5));
     for (size_t i = 0; i < wh.size(); ++i) wh[i] = T(0.5) * T(pl->window[i / reps]);  // exact scaling of the window in T
-    if ((st = upload<T>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
-    return upload<T>(pl, &pl->d_ones_half, oh);
+    if ((st = upload_raw<T>(pl, &pl->d_window_half, wh)) != SGX_OK) return st;
+    return upload_raw<T>(pl, &pl->d_ones_half, oh);
 }
 
 // Band schedule of the tuned f32 kernel (n_fft 1024, and 512 in its two-frames-per-transform mode), built on the HOST at plan
@@ -742,12 +696,12 @@ template <typename T>
 sgx_status build_device_tables(sgx_plan *pl) {
     const unsigned n = pl->p.n_fft;
     sgx_status st;
-    if ((st = upload_cast<T>(pl, &pl->d_window, pl->window)) != SGX_OK) return st;
-    if ((st = upload<T>(pl, &pl->d_tw, twiddle_vector<T>(n, -2.0, n))) != SGX_OK) return st;  // tw[k] = exp(-2 pi i k / n)
+    if ((st = upload(pl, &pl->d_window, pl->window, pl->dtype)) != SGX_OK) return st;
+    if ((st = upload_raw<T>(pl, &pl->d_tw, twiddle_vector<T>(n, -2.0, n))) != SGX_OK) return st;  // tw[k] = exp(-2 pi i k / n)
     if (pl->out_mode == OUT_MEL) {
-        if ((st = upload<uint32_t>(pl, &pl->d_mel_ptr, pl->mel_ptr)) != SGX_OK) return st;
-        if ((st = upload<uint32_t>(pl, &pl->d_mel_col, pl->mel_col)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->d_mel_val, pl->mel_val)) != SGX_OK) return st;
+        if ((st = upload_raw<uint32_t>(pl, &pl->d_mel_ptr, pl->mel_ptr)) != SGX_OK) return st;
+        if ((st = upload_raw<uint32_t>(pl, &pl->d_mel_col, pl->mel_col)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_mel_val, pl->mel_val, pl->dtype)) != SGX_OK) return st;
         // triangular bands are contiguous column runs; build a 4-wide padded copy (4-element
         // aligned column groups, zero weights outside the true band) so the reduction reads LDS 16 bytes at a time
         if (pl->mel_contig) {
@@ -764,9 +718,9 @@ sgx_status build_device_tables(sgx_plan *pl) {
             }
             pptr[pl->p.n_mels] = uint32_t(pw.size() / 4);
             pl->mel_pchunks = uint32_t(pw.size() / 4);
-            if ((st = upload<uint32_t>(pl, &pl->d_mel_pptr, pptr)) != SGX_OK) return st;
-            if ((st = upload<uint32_t>(pl, &pl->d_mel_pcol, pcol)) != SGX_OK) return st;
-            if ((st = upload<T>(pl, &pl->d_mel_pw, pw)) != SGX_OK) return st;
+            if ((st = upload_raw<uint32_t>(pl, &pl->d_mel_pptr, pptr)) != SGX_OK) return st;
+            if ((st = upload_raw<uint32_t>(pl, &pl->d_mel_pcol, pcol)) != SGX_OK) return st;
+            if ((st = upload_raw<T>(pl, &pl->d_mel_pw, pw)) != SGX_OK) return st;
         }
         // Matrix-core epilogue of the tuned kernel (f32, n_fft = 1024): banks with wide rows (the dense ERB bank, very coarse
         // Mel banks) are applied as [16 rows x K] x [K x 16 frames] products on v_mfma_f32_16x16x4_f32, K restricted to the
@@ -819,12 +773,12 @@ sgx_status build_device_tables(sgx_plan *pl) {
             }
             frag.resize(frag.size() + 4 * 256, 0.0f);  // the kernel's 4-deep fragment ring prefetches unguarded
             pl->mm_nblk = nblk;
-            if ((st = upload<float>(pl, &pl->d_mm_frag, frag)) != SGX_OK) return st;
-            if ((st = upload<uint32_t>(pl, &pl->d_mm_blk, blk)) != SGX_OK) return st;
+            if ((st = upload_raw<float>(pl, &pl->d_mm_frag, frag)) != SGX_OK) return st;
+            if ((st = upload_raw<uint32_t>(pl, &pl->d_mm_blk, blk)) != SGX_OK) return st;
         }
         // Band schedule of the tuned kernel: built on the host at plan creation (build_band_schedule), uploaded here
         if (kind_is_tuned(pl->kind) && !pl->h_mel_sched.empty() && !pl->d_mm_frag) {
-            if ((st = upload<uint32_t>(pl, &pl->d_mel_sched, pl->h_mel_sched)) != SGX_OK) return st;
+            if ((st = upload_raw<uint32_t>(pl, &pl->d_mel_sched, pl->h_mel_sched)) != SGX_OK) return st;
         }
     }
     if (pl->p.n_mfcc > 0) {
@@ -835,8 +789,8 @@ sgx_status build_device_tables(sgx_plan *pl) {
         if (pl->p.mfcc_lifter > 0)
             for (unsigned i = 0; i < nc; ++i)
                 lift[i] = std::fma(double(pl->p.mfcc_lifter) / 2.0, std::sin(kPi * double(i) / double(pl->p.mfcc_lifter)), 1.0);
-        if ((st = upload_cast<T>(pl, &pl->d_dct, basis)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->d_lifter, lift)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_dct, basis, pl->dtype)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_lifter, lift, pl->dtype)) != SGX_OK) return st;
         // Fused epilogue of the tuned f32 kernel at n_fft 1024 (kernels_r32x16.hip mfcc_tile): the basis as matrix-core A-operands with a
         // lane's steps contiguous, frag[mt][lane][s] = basis[16 mt + (l & 15)][4 s + (l >> 4)] in rows of RL floats (zero beyond n_mfcc /
         // n_mels), then the lifter weights.  Needs the band schedule (Mel-dB tile in LDS), at most 96 bands (the tile sits between the staged
@@ -855,7 +809,7 @@ sgx_status build_device_tables(sgx_plan *pl) {
             for (unsigned c = 0; c < ((nc + 3) & ~3u); ++c) frag[size_t(mtiles) * 64 * RL + c] = c < nc ? float(lift[c]) : 1.0f;
             const size_t lds = size_t(r32x16::kLdsBytes) - size_t(r32x16::kMelMaxWords) * 4 + ((pl->mel_sched_words + 3u) & ~3u) * 4 + frag.size() * 4 + 64;
             if (lds <= 163840) {
-                if ((st = upload<float>(pl, &pl->d_mfcc_frag, frag)) != SGX_OK) return st;
+                if ((st = upload_raw<float>(pl, &pl->d_mfcc_frag, frag)) != SGX_OK) return st;
                 pl->mfcc_frag_words = unsigned(frag.size());
                 pl->mfcc_steps = steps;
                 pl->mfcc_mtiles = mtiles;
@@ -866,13 +820,13 @@ sgx_status build_device_tables(sgx_plan *pl) {
         if ((st = tuned_tables<T>(pl, *k)) != SGX_OK) return st;
     if (pl->kind == K_BIGFFT) {  // global-memory transforms (bigfft.hip): stage twiddles, the two-level W_M table, chirp + transformed chirp
         BigHost h;
-        if (!big_host_tables(n, h)) return set_err(pl, SGX_INTERNAL, "Internal error: K_BIGFFT plan at an unsupported length");
-        SGX_HIP(pl, big_upload(h, pl->dtype, pl->big));
+        if (!big_host_tables(n, h)) return fail(pl, SGX_INTERNAL, "Internal error: K_BIGFFT plan at an unsupported length");
+        SGX_TRY_HIP(pl, big_upload(h, pl->dtype, pl->big));
     }
     if (pl->kind == K_BLUESTEIN && pl->bs_fwd_half) {  // half-length complex form: tables of length n / 2 (shared with the inverse rows)
         BsHostTables h;
-        if (!bluestein_host_tables(n / 2, pl->dtype, h)) return set_err(pl, SGX_INTERNAL, "Internal error: chirp-z plan without a pass split");
-        if ((st = upload_bs<T>(pl, pl->bs_half, h)) != SGX_OK) return st;
+        if (!bluestein_host_tables(n / 2, pl->dtype, h)) return fail(pl, SGX_INTERNAL, "Internal error: chirp-z plan without a pass split");
+        if ((st = upload_bs(pl, pl->bs_half, h, pl->dtype)) != SGX_OK) return st;
     } else if (pl->kind == K_BLUESTEIN) {  // chirp-z tables (bluestein.hip), evaluated in f64
         const unsigned M = pl->bs_M;
         // c_j = e^(+i pi j^2 / n): the angle is reduced in integers, j^2 mod 2 n, so that a large j loses nothing
@@ -920,7 +874,7 @@ sgx_status build_device_tables(sgx_plan *pl) {
             twm[2 * k + 1] = std::sin(a);
         }
         unsigned fa = 0, fb = 0, fc = 0;
-        if (!bluestein_fused_split(M, pl->dtype, &fa, &fb, &fc)) return set_err(pl, SGX_INTERNAL, "Internal error: chirp-z plan without a pass split");
+        if (!bluestein_fused_split(M, pl->dtype, &fa, &fb, &fc)) return fail(pl, SGX_INTERNAL, "Internal error: chirp-z plan without a pass split");
         // window and chirp as one table; FFT_M(b) / M in the order the kernel's product step reads it — [k3][k1][k2] for bin
         // k1 + A (k2 + B k3), [k2][k1] for the two-pass splits
         std::vector<double> wc(2 * size_t(n)), bp(2 * size_t(M));
@@ -934,10 +888,10 @@ sgx_status build_device_tables(sgx_plan *pl) {
             bp[2 * at] = bh[2 * k];
             bp[2 * at + 1] = bh[2 * k + 1];
         }
-        if ((st = upload_cast<T>(pl, &pl->d_bs_chirp, cc)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->d_bs_tw, twm)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->d_bs_wc, wc)) != SGX_OK) return st;
-        if ((st = upload_cast<T>(pl, &pl->d_bs_bhp, bp)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_bs_chirp, cc, pl->dtype)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_bs_tw, twm, pl->dtype)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_bs_wc, wc, pl->dtype)) != SGX_OK) return st;
+        if ((st = upload(pl, &pl->d_bs_bhp, bp, pl->dtype)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
@@ -1024,7 +978,7 @@ hipError_t launch(sgx_plan *pl, const StftArgs &a, KernelKind kind, hipStream_t 
     switch (kind) {
     case K_BIGFFT: {  // sequence scratch: sized by sgx_reserve, else grown here
         const size_t need = big_scratch_bytes(pl->big, pl->dtype, size_t(a.batch) * ((a.n_frames + 1u) / 2u));
-        if (grow(pl, &pl->d_big, &pl->d_big_bytes, need) != SGX_OK) return hipErrorOutOfMemory;
+        if (grow(pl, pl->d_big, need) != SGX_OK) return hipErrorOutOfMemory;
         return launch_big_stft(pl->big, a, pl->d_big, pl->dtype, s);
     }
     case K_BLUESTEIN: return launch_bluestein_plan(pl, a, s);
@@ -1038,18 +992,18 @@ hipError_t launch(sgx_plan *pl, const StftArgs &a, KernelKind kind, hipStream_t 
 sgx_status check_call(sgx_plan *pl, const void *samples, size_t batch, size_t n_samples, size_t stride,
                       void *out, size_t out_elems, size_t *n_frames_out) {
     if (!pl) return SGX_INVALID_INPUT;
-    if (!samples || !out) return set_err(pl, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (!samples || !out) return fail(pl, SGX_INVALID_INPUT, "Invalid input: null buffer");
     if (batch == 0 || n_samples == 0)
-        return set_err(pl, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");  // NonEmptySlice
-    if (stride < n_samples) return set_err(pl, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
-    if (batch > 0xffffffffull) return set_err(pl, SGX_INVALID_INPUT, "Invalid input: batch too large");
+        return fail(pl, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");  // NonEmptySlice
+    if (stride < n_samples) return fail(pl, SGX_INVALID_INPUT, "Invalid input: sample_stride < n_samples");
+    if (batch > 0xffffffffull) return fail(pl, SGX_INVALID_INPUT, "Invalid input: batch too large");
     const size_t nf = frame_count(pl->p, n_samples);
-    if (nf > 0x7fffffffull) return set_err(pl, SGX_INVALID_INPUT, "Invalid input: too many frames");
+    if (nf > 0x7fffffffull) return fail(pl, SGX_INVALID_INPUT, "Invalid input: too many frames");
     const size_t expect = batch * size_t(pl->n_final) * nf * (pl->out_mode == OUT_COMPLEX ? 2 : 1);
     if (out_elems != expect)  // compute_into: DimensionMismatch{expected, got} (:423-434)
-        return dim_err(pl, expect, out_elems);
+        return dim_mismatch(pl, expect, out_elems);
     if (!pl->device_ready)
-        return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return fail(pl, SGX_BACKEND, kNoDeviceText);
     *n_frames_out = nf;
     return SGX_OK;
 }
@@ -1081,16 +1035,16 @@ int chain_pos(KernelKind k) { return kind_is_tuned(k) ? 0 : k == K_REG_RADIX ? 1
 // `iters` rounds of `launches` on stream s; with `ms`, the plan's events around them give the time per round
 template <typename F>
 sgx_status run_timed(sgx_plan *pl, hipStream_t s, int iters, float *ms, F launches) {
-    if (ms) SGX_HIP(pl, hipEventRecord(pl->ev0, s));
+    if (ms) SGX_TRY_HIP(pl, hipEventRecord(pl->ev0, s));
     for (int i = 0; i < iters; ++i) {
         const sgx_status st = launches();
         if (st != SGX_OK) return st;
     }
     if (ms) {
-        SGX_HIP(pl, hipEventRecord(pl->ev1, s));
-        SGX_HIP(pl, hipEventSynchronize(pl->ev1));
+        SGX_TRY_HIP(pl, hipEventRecord(pl->ev1, s));
+        SGX_TRY_HIP(pl, hipEventSynchronize(pl->ev1));
         float t = 0.f;
-        SGX_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
+        SGX_TRY_HIP(pl, hipEventElapsedTime(&t, pl->ev0, pl->ev1));
         *ms = t / float(iters);
     }
     return SGX_OK;
@@ -1117,7 +1071,7 @@ sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, 
     a.amp = pl->amp;
     a.eps = pl->eps;
     return run_timed(pl, s, iters, ms, [&]() -> sgx_status {
-        SGX_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
+        SGX_TRY_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
         return SGX_OK;
     });
 }
@@ -1141,7 +1095,7 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
         mfcc_fused = resolve_geometry(pl, probe, k2) && k2 == K_R32X16_F32;
     }
     if (mfcc && !mfcc_fused) {
-        sgx_status st = grow(pl, &pl->d_melbuf, &pl->d_melbuf_bytes, batch * size_t(pl->n_out) * n_frames * pl->elem);
+        sgx_status st = grow(pl, pl->d_melbuf, batch * size_t(pl->n_out) * n_frames * pl->elem);
         if (st != SGX_OK) return st;
         stage_out = pl->d_melbuf;
     }
@@ -1161,21 +1115,21 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
     StftArgs a1 = a;  // the first (or only) launch
     const bool split_bank = pl->split_bank;
     if (split_bank) {
-        sgx_status st = grow(pl, &pl->d_pwbuf, &pl->d_pwbuf_bytes, batch * size_t(pl->nb_fft) * n_frames * pl->elem);
+        sgx_status st = grow(pl, pl->d_pwbuf, batch * size_t(pl->nb_fft) * n_frames * pl->elem);
         if (st != SGX_OK) return st;
         per_bin_args(pl, a1);
         a1.out = pl->d_pwbuf;
     }
     if (!resolve_geometry(pl, a1, kind))
-        return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
+        return fail(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
     if (kind_is_tuned(kind)) a1.window = pl->d_window_half;
     const sgx_status st = run_timed(pl, s, iters, ms, [&]() -> sgx_status {
-        SGX_HIP(pl, launch(pl, a1, kind, s));
-        if (split_bank) SGX_HIP(pl, launch_bank_rows(pl->d_pwbuf, stage_out, a, pl->dtype, s));
+        SGX_TRY_HIP(pl, launch(pl, a1, kind, s));
+        if (split_bank) SGX_TRY_HIP(pl, launch_bank_rows(pl->d_pwbuf, stage_out, a, pl->dtype, s));
         if (pl->p.freq_scale == SGX_FREQ_CHROMA)
-            SGX_HIP(pl, launch_chroma_norm(out, unsigned(batch), unsigned(n_frames), pl->p.chroma_norm, pl->dtype, s));
+            SGX_TRY_HIP(pl, launch_chroma_norm(out, unsigned(batch), unsigned(n_frames), pl->p.chroma_norm, pl->dtype, s));
         if (mfcc)
-            SGX_HIP(pl, launch_mfcc(pl->d_melbuf, out, pl->d_dct, pl->d_lifter, unsigned(batch), pl->p.n_mels, unsigned(n_frames),
+            SGX_TRY_HIP(pl, launch_mfcc(pl->d_melbuf, out, pl->d_dct, pl->d_lifter, unsigned(batch), pl->p.n_mels, unsigned(n_frames),
                                     pl->p.n_mfcc, skip, pl->p.mfcc_lifter > 0, pl->dtype, s));
         return SGX_OK;
     });
@@ -1187,11 +1141,11 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
 
 void free_device(sgx_plan *pl) {
     void **bufs[] = {&pl->d_window, &pl->d_tw, &pl->d_tw1, &pl->d_tw2, &pl->d_mel_ptr, &pl->d_mel_col,
-                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_melbuf, &pl->d_pwbuf, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_frames, &pl->d_flag, &pl->d_ones, &pl->d_in, &pl->d_out, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->bs_half.chirp, &pl->bs_half.bhp, &pl->bs_half.tw, &pl->d_cqt_tab, &pl->d_cqt_info, &pl->d_cqt_len};
+                     &pl->d_mel_val, &pl->d_dct, &pl->d_lifter, &pl->d_mfcc_frag, &pl->d_mel_pptr, &pl->d_mel_pcol, &pl->d_mel_pw, &pl->d_mm_frag, &pl->d_mm_blk, &pl->d_mel_sched, &pl->d_itw, &pl->d_itwr, &pl->d_itw1, &pl->d_flag, &pl->d_ones, &pl->d_window_half, &pl->d_ones_half, &pl->d_bs_chirp, &pl->d_bs_tw, &pl->d_bs_wc, &pl->d_bs_bhp, &pl->d_cqt_tab, &pl->d_cqt_info, &pl->d_cqt_len};
     for (void **b : bufs)
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     big_free(pl->big);
-    if (pl->d_big) { (void)hipFree(pl->d_big); pl->d_big = nullptr; pl->d_big_bytes = 0; }
+    bs_free(pl->bs_half);
     if (pl->ev0) (void)hipEventDestroy(pl->ev0);
     if (pl->ev1) (void)hipEventDestroy(pl->ev1);
     pl->ev0 = pl->ev1 = nullptr;
@@ -1283,19 +1237,19 @@ sgx_status inverse_tables(sgx_plan *pl) {
     if (pl->d_itw || pl->d_flag) return SGX_OK;
     const size_t n = pl->p.n_fft;
     if (pl->kind == K_BIGFFT) {  // the inverse runs on the forward tables (bigfft.hip): only the DC / Nyquist flag word
-        SGX_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
+        SGX_TRY_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
         return SGX_OK;
     }
-    sgx_status st = upload<T>(pl, &pl->d_itw, twiddle_vector<T>(unsigned(n), -2.0, unsigned(n)));
+    sgx_status st = upload_raw<T>(pl, &pl->d_itw, twiddle_vector<T>(unsigned(n), -2.0, unsigned(n)));
     if (st != SGX_OK) return st;
     // The two lengths whose forward frames fit the LDS radix-2 kernel (half-length complex form) while no tile holds a full-length row
     // of the inverse (f32 32768, f64 16384): the inverse rows go through global memory, as a K_BIGFFT plan's do.  (Before: sgx_istft
     // and sgx_c2r returned "n_fft too large for the on-chip frame tile" there.)
     if (c2r_tile_for(unsigned(n), pl->dtype, kC2rLds) == 0 && big_supported(n)) {
         BigHost h;
-        if (!big_host_tables(unsigned(n), h)) return set_err(pl, SGX_INTERNAL, "Internal error: no global-memory transform for the inverse rows");
-        SGX_HIP(pl, big_upload(h, pl->dtype, pl->big));
-        if ((st = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return st;  // one sequence: sgx_c2r
+        if (!big_host_tables(unsigned(n), h)) return fail(pl, SGX_INTERNAL, "Internal error: no global-memory transform for the inverse rows");
+        SGX_TRY_HIP(pl, big_upload(h, pl->dtype, pl->big));
+        if ((st = grow(pl, pl->d_big, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return st;  // one sequence: sgx_c2r
     }
     // Even lengths whose rows have neither a register-tiled split (n / 2) nor a chirp-z convolution of their own in LDS (f64 above
     // 4096, f32 above 8192) invert through the chirp-z kernel in half-length complex form: tables of length n / 2.  (Before: the
@@ -1311,14 +1265,14 @@ sgx_status inverse_tables(sgx_plan *pl) {
         const bool own_fits = Mfull <= 16384ull && bluestein_fused_split(unsigned(Mfull), pl->dtype, &fa, &fb, &fc);
         if (!pl->bs_half.M && !own_fits && n >= 32 && n <= 32768 && n % 2 == 0 && (n & (n - 1)) != 0 && !pl->d_bs_bhp &&
             !reg_split_len(unsigned(n / 2), pl->dtype, &fa, &fb, &fc) && bluestein_host_tables(unsigned(n / 2), pl->dtype, h)) {
-            if ((st = upload_bs<T>(pl, pl->bs_half, h)) != SGX_OK) return st;
+            if ((st = upload_bs(pl, pl->bs_half, h, pl->dtype)) != SGX_OK) return st;
         }
     }
     if (const FusedInverse *f = fused_inverse_of(pl)) {
-        if (f->twr && (st = upload<T>(pl, &pl->d_itwr, twiddle_vector<T>(unsigned(n / 2), 2.0, unsigned(n)))) != SGX_OK) return st;
-        if ((st = upload<T>(pl, &pl->d_itw1, twiddle_grid<T>(f->tw1_rows, f->tw1_cols))) != SGX_OK) return st;
+        if (f->twr && (st = upload_raw<T>(pl, &pl->d_itwr, twiddle_vector<T>(unsigned(n / 2), 2.0, unsigned(n)))) != SGX_OK) return st;
+        if ((st = upload_raw<T>(pl, &pl->d_itw1, twiddle_grid<T>(f->tw1_rows, f->tw1_cols))) != SGX_OK) return st;
     }
-    SGX_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
+    SGX_TRY_HIP(pl, hipMalloc(&pl->d_flag, sizeof(unsigned)));
     return SGX_OK;
 }
 
@@ -1340,14 +1294,14 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
         c.scale = inverse_scale(pl);
         c.win = win;
         c.bad_flag = (unsigned *)pl->d_flag;
-        sgx_status st = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, batch * ((n_frames + 1) / 2)));
+        sgx_status st = grow(pl, pl->d_big, big_scratch_bytes(pl->big, pl->dtype, batch * ((n_frames + 1) / 2)));
         if (st != SGX_OK) return st;
-        SGX_HIP(pl, launch_big_c2r(pl->big, c, pl->d_big, pl->dtype, s));
+        SGX_TRY_HIP(pl, launch_big_c2r(pl->big, c, pl->d_big, pl->dtype, s));
         *route = "big";
         return SGX_OK;
     }
     c.tile = c2r_tile_for(n, pl->dtype, kC2rLds);
-    if (c.tile == 0) return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
+    if (c.tile == 0) return fail(pl, SGX_BACKEND, "hip -- FFT backend error: n_fft too large for the on-chip frame tile");
     c.tiles = unsigned((n_frames + c.tile - 1) / c.tile);
     c.tw = pl->d_itw;
     c.scale = inverse_scale(pl);
@@ -1373,7 +1327,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
         r = "c2r_rows";
         e = launch_c2r_rows(c, pl->dtype, s);
     }
-    SGX_HIP(pl, e);
+    SGX_TRY_HIP(pl, e);
     *route = r;
     return SGX_OK;
 }
@@ -1385,13 +1339,13 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
                      const char **route) {
     sgx_status st;
     const size_t n = pl->p.n_fft;
-    SGX_HIP(pl, hipMemsetAsync(pl->d_flag, 0, sizeof(unsigned), s));
+    SGX_TRY_HIP(pl, hipMemsetAsync(pl->d_flag, 0, sizeof(unsigned), s));
     const size_t pad = pl->p.centre ? n / 2 : 0;
     const size_t full = (n_frames - 1) * size_t(pl->p.hop_size) + n;
     const size_t start = out_len == full ? 0 : pad;  // untrimmed when the centred signal would be empty (:4933)
     const InverseRoute r = inverse_route(pl, batch, n_frames, false);
     if (r.tuned) {
-        SGX_HIP(pl, r.tuned->launch(pl, InverseCall{spec, out, unsigned(n_frames), unsigned(batch), start, out_len, s}));
+        SGX_TRY_HIP(pl, r.tuned->launch(pl, InverseCall{spec, out, unsigned(n_frames), unsigned(batch), start, out_len, s}));
         *route = r.tuned->route;
         return SGX_OK;
     }
@@ -1402,12 +1356,12 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
             *route = "istft_reg";
             return SGX_OK;
         }
-        if (e != hipErrorNotSupported) SGX_HIP(pl, e);
+        if (e != hipErrorNotSupported) SGX_TRY_HIP(pl, e);
     }
-    if ((st = grow(pl, &pl->d_frames, &pl->d_frames_bytes, batch * n_frames * n * pl->elem)) != SGX_OK) return st;
+    if ((st = grow(pl, pl->d_frames, batch * n_frames * n * pl->elem)) != SGX_OK) return st;
     const char *rows = "";
     if ((st = launch_c2r_frames(pl, spec, pl->d_frames, batch, n_frames, true, pl->d_window, s, &rows)) != SGX_OK) return st;
-    SGX_HIP(pl, launch_istft_ola(pl->d_frames, pl->d_window, out, unsigned(n), pl->p.hop_size, unsigned(n_frames), start, out_len,
+    SGX_TRY_HIP(pl, launch_istft_ola(pl->d_frames, pl->d_window, out, unsigned(n), pl->p.hop_size, unsigned(n_frames), start, out_len,
                                  unsigned(batch), pl->dtype, s));
     static const char *const with_ola[][2] = {{"c2r_reg", "c2r_reg+ola"}, {"c2r_chirpz", "c2r_chirpz+ola"},
                                               {"c2r_chirpz_half", "c2r_chirpz_half+ola"}, {"c2r_rows", "c2r_rows+ola"}, {"big", "big+ola"}};
@@ -1418,10 +1372,10 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
 
 sgx_status check_flag(sgx_plan *pl, hipStream_t s) {
     unsigned flag = 0;
-    SGX_HIP(pl, hipMemcpyAsync(&flag, pl->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    SGX_HIP(pl, hipStreamSynchronize(s));
+    SGX_TRY_HIP(pl, hipMemcpyAsync(&flag, pl->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(pl, hipStreamSynchronize(s));
     if (flag)  // realfft: FftError::InputValues, mapped at fft_backend.rs:555-557
-        return set_err(pl, SGX_BACKEND, "hip -- FFT backend error: imaginary part of the DC or Nyquist bin is non-zero");
+        return fail(pl, SGX_BACKEND, "hip -- FFT backend error: imaginary part of the DC or Nyquist bin is non-zero");
     return SGX_OK;
 }
 
@@ -1434,7 +1388,7 @@ sgx_plan *new_plan(const sgx_params &params) {
     if (params.window_kind == SGX_WIN_CUSTOM) pl->custom_window.assign(params.custom_window, params.custom_window + params.n_fft);
     pl->p.custom_window = nullptr;
     pl->dtype = params.dtype;
-    pl->elem = params.dtype == SGX_F64 ? 8 : 4;
+    pl->elem = elem_size(params.dtype);
     pl->nb_fft = params.n_fft / 2 + 1;
     pl->amp = params.amp_scale == SGX_AMP_MAGNITUDE ? AMP_MAGNITUDE
               : (params.amp_scale == SGX_AMP_DECIBELS && params.has_log_params) ? AMP_DB : AMP_POWER;
@@ -1463,14 +1417,14 @@ sgx_status open_plan(sgx_plan *pl, sgx_plan **out, sgx_status (*init)(sgx_plan *
         pl->device = dev;
         DeviceGuard dg;
         auto dev_init = [&]() -> sgx_status {
-            SGX_HIP(pl, dg.enter(dev));
-            SGX_HIP(pl, hipEventCreate(&pl->ev0));
-            SGX_HIP(pl, hipEventCreate(&pl->ev1));
+            SGX_TRY_HIP(pl, dg.enter(dev));
+            SGX_TRY_HIP(pl, hipEventCreate(&pl->ev0));
+            SGX_TRY_HIP(pl, hipEventCreate(&pl->ev1));
             return init(pl);
         };
         const sgx_status st = dev_init();
         if (st != SGX_OK) {
-            g_create_err = pl->err;
+            create_err<sgx_plan>() = pl->err;
             free_device(pl);
             delete pl;
             return st;
@@ -1493,8 +1447,8 @@ int32_t sgx_device_count(void) {
     return n;
 }
 
-const char *sgx_last_create_error(void) { return g_create_err.c_str(); }
-const char *sgx_last_error(const sgx_plan *plan) { return plan ? plan->err.c_str() : g_create_err.c_str(); }
+const char *sgx_last_create_error(void) { return create_err<sgx_plan>().c_str(); }
+const char *sgx_last_error(const sgx_plan *plan) { return plan ? plan->err.c_str() : create_err<sgx_plan>().c_str(); }
 
 const char *sgx_istft_kernel_name(const sgx_plan *plan) { return plan ? plan->istft_route : ""; }
 
@@ -1655,11 +1609,11 @@ sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
         // that `process` never allocates (src/fft_backend.rs:21-24): one frame of staging each way, the rectangular window,
         // the inverse tables and the DC/Nyquist flag.  Batched calls size their scratch through sgx_reserve.
         const size_t frame_bytes = 2 * size_t(pl->nb_fft) * pl->elem;
-        if (pl->kind == K_BIGFFT && (s2 = grow(pl, &pl->d_big, &pl->d_big_bytes, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return s2;  // one sequence: the per-frame entry points
-        if ((s2 = grow(pl, &pl->d_in, &pl->d_in_bytes, frame_bytes)) != SGX_OK) return s2;
-        if ((s2 = grow(pl, &pl->d_out, &pl->d_out_bytes, frame_bytes)) != SGX_OK) return s2;
+        if (pl->kind == K_BIGFFT && (s2 = grow(pl, pl->d_big, big_scratch_bytes(pl->big, pl->dtype, 1))) != SGX_OK) return s2;  // one sequence: the per-frame entry points
+        if ((s2 = grow(pl, pl->d_in, frame_bytes)) != SGX_OK) return s2;
+        if ((s2 = grow(pl, pl->d_out, frame_bytes)) != SGX_OK) return s2;
         std::vector<double> ones(pl->p.n_fft, 1.0);
-        s2 = pl->dtype == SGX_F64 ? upload_cast<double>(pl, &pl->d_ones, ones) : upload_cast<float>(pl, &pl->d_ones, ones);
+        s2 = upload(pl, &pl->d_ones, ones, pl->dtype);
         if (s2 != SGX_OK) return s2;
         return pl->dtype == SGX_F64 ? inverse_tables<double>(pl) : inverse_tables<float>(pl);
     });
@@ -1691,7 +1645,7 @@ sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *c
 
 sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->kind != K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: plan is not a CQT plan");
+    if (plan->kind != K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: plan is not a CQT plan");
     if (total) *total = plan->cqt_re.size();
     if (lengths) std::copy(plan->cqt_len.begin(), plan->cqt_len.end(), lengths);
     if (re) std::copy(plan->cqt_re.begin(), plan->cqt_re.end(), re);
@@ -1701,8 +1655,8 @@ sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *length
 
 void sgx_plan_destroy(sgx_plan *plan) {
     if (!plan) return;
+    DeviceGuard dg;  // the plan's buffers are freed on its device
     if (plan->device_ready) {
-        DeviceGuard dg;
         (void)dg.enter(plan->device);
         free_device(plan);
     }
@@ -1711,7 +1665,7 @@ void sgx_plan_destroy(sgx_plan *plan) {
 
 sgx_status sgx_output_shape(const sgx_plan *plan, size_t n_samples, size_t *n_bins, size_t *n_frames) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (n_samples == 0) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: signal length must be non-zero");
+    if (n_samples == 0) return fail(plan, SGX_INVALID_INPUT, "Invalid input: signal length must be non-zero");
     if (n_bins) *n_bins = plan->n_final;
     if (n_frames) *n_frames = frame_count(plan->p, n_samples);
     return SGX_OK;
@@ -1723,20 +1677,20 @@ sgx_status sgx_execute(sgx_plan *plan, const void *samples, size_t batch, size_t
     sgx_status st = check_call(plan, samples, batch, n_samples, sample_stride, out, out_elems, &nf);
     if (st != SGX_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+    if (mem_kind != SGX_MEM_HOST && mem_kind != SGX_MEM_DEVICE) return fail(plan, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));
+    SGX_TRY_HIP(plan, dg.enter(plan->device));
     if (mem_kind == SGX_MEM_DEVICE) return run_device(plan, samples, batch, n_samples, sample_stride, out, nf, s, 1, nullptr);
     // host pointers: plan-owned staging (sized by sgx_reserve, else grown on demand; reused across calls), synchronous
     const size_t in_bytes = ((batch - 1) * sample_stride + n_samples) * plan->elem;
     const size_t out_bytes = out_elems * plan->elem;
-    if ((st = grow(plan, &plan->d_in, &plan->d_in_bytes, in_bytes)) != SGX_OK) return st;
-    if ((st = grow(plan, &plan->d_out, &plan->d_out_bytes, out_bytes)) != SGX_OK) return st;
-    SGX_HIP(plan, hipMemcpyAsync(plan->d_in, samples, in_bytes, hipMemcpyHostToDevice, s));
+    if ((st = grow(plan, plan->d_in, in_bytes)) != SGX_OK) return st;
+    if ((st = grow(plan, plan->d_out, out_bytes)) != SGX_OK) return st;
+    SGX_TRY_HIP(plan, hipMemcpyAsync(plan->d_in, samples, in_bytes, hipMemcpyHostToDevice, s));
     if ((st = run_device(plan, plan->d_in, batch, n_samples, sample_stride, plan->d_out, nf, s, 1, nullptr)) != SGX_OK)
         return st;
-    SGX_HIP(plan, hipMemcpyAsync(out, plan->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    SGX_HIP(plan, hipStreamSynchronize(s));
+    SGX_TRY_HIP(plan, hipMemcpyAsync(out, plan->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(plan, hipStreamSynchronize(s));
     return SGX_OK;
 }
 
@@ -1746,9 +1700,9 @@ sgx_status sgx_execute_timed(sgx_plan *plan, const void *samples, size_t batch, 
     size_t nf = 0;
     sgx_status st = check_call(plan, samples, batch, n_samples, sample_stride, out, out_elems, &nf);
     if (st != SGX_OK) return st;
-    if (iters < 1 || !ms_per_launch) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: iters must be >= 1");
+    if (iters < 1 || !ms_per_launch) return fail(plan, SGX_INVALID_INPUT, "Invalid input: iters must be >= 1");
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));
+    SGX_TRY_HIP(plan, dg.enter(plan->device));
     return run_device(plan, samples, batch, n_samples, sample_stride, out, nf, static_cast<hipStream_t>(hip_stream),
                       iters, ms_per_launch);
 }
@@ -1784,18 +1738,18 @@ sgx_status sgx_axes(const sgx_plan *plan, size_t n_frames, double *freqs, double
 
 sgx_status sgx_r2c(sgx_plan *plan, const void *in, size_t in_len, void *out, size_t out_len) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
-    if (!in || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (plan->kind == K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
+    if (!in || !out) return fail(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
     const size_t n = plan->p.n_fft, nb = plan->nb_fft;
     if (in_len != n)  // validate_fft_io src/fft_backend.rs:264-282
-        return dim_err(plan, n, in_len);
+        return dim_mismatch(plan, n, in_len);
     if (out_len != nb)
-        return dim_err(plan, nb, out_len);
+        return dim_mismatch(plan, nb, out_len);
     if (!plan->device_ready)
-        return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return fail(plan, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));  // staging, window of ones: allocated at plan creation
-    SGX_HIP(plan, hipMemcpy(plan->d_in, in, n * plan->elem, hipMemcpyHostToDevice));
+    SGX_TRY_HIP(plan, dg.enter(plan->device));  // staging, window of ones: allocated at plan creation
+    SGX_TRY_HIP(plan, hipMemcpy(plan->d_in, in, n * plan->elem, hipMemcpyHostToDevice));
     StftArgs a;
     fill_args(plan, a, plan->d_in, plan->d_out, 1, n, n, 1);
     a.window = plan->d_ones;
@@ -1805,17 +1759,17 @@ sgx_status sgx_r2c(sgx_plan *plan, const void *in, size_t in_len, void *out, siz
     a.amp = AMP_POWER;
     KernelKind kind = plan->kind;
     if (!resolve_geometry(plan, a, kind))  // (down the chain: a single frame leaves the tuned kernels' multi-frame tiles for the register-tiled kernel)
-        return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: n_fft too large");
+        return fail(plan, SGX_BACKEND, "hip -- FFT backend error: n_fft too large");
     if (kind_is_tuned(kind)) a.window = plan->d_ones_half;
-    SGX_HIP(plan, launch(plan, a, kind, nullptr));
-    SGX_HIP(plan, hipMemcpy(out, plan->d_out, 2 * nb * plan->elem, hipMemcpyDeviceToHost));
+    SGX_TRY_HIP(plan, launch(plan, a, kind, nullptr));
+    SGX_TRY_HIP(plan, hipMemcpy(out, plan->d_out, 2 * nb * plan->elem, hipMemcpyDeviceToHost));
     return SGX_OK;
 }
 
 // ---- inverse path entry points (helpers above the extern "C" block)
 sgx_status sgx_istft_length(const sgx_plan *plan, size_t n_frames, size_t *n_samples) {
     if (!plan || !n_samples) return SGX_INVALID_INPUT;
-    if (n_frames == 0) return set_err(const_cast<sgx_plan *>(plan), SGX_INVALID_INPUT, "Invalid input: stft matrix must be non-empty");
+    if (n_frames == 0) return fail(const_cast<sgx_plan *>(plan), SGX_INVALID_INPUT, "Invalid input: stft matrix must be non-empty");
     *n_samples = istft_length(plan->p, n_frames);
     return SGX_OK;
 }
@@ -1823,19 +1777,19 @@ sgx_status sgx_istft_length(const sgx_plan *plan, size_t n_frames, size_t *n_sam
 sgx_status sgx_istft(sgx_plan *plan, const void *stft, size_t batch, size_t n_bins, size_t n_frames, void *out,
                      size_t out_elems, int32_t mem_kind, void *hip_stream) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
-    if (!stft || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
-    if (batch == 0 || n_frames == 0) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: stft matrix must be non-empty");
+    if (plan->kind == K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
+    if (!stft || !out) return fail(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (batch == 0 || n_frames == 0) return fail(plan, SGX_INVALID_INPUT, "Invalid input: stft matrix must be non-empty");
     if (n_bins != plan->nb_fft)  // :4876-4879
-        return dim_err(plan, plan->nb_fft, n_bins);
-    if (batch > 65535 || n_frames > 0x7fffffffull) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
+        return dim_mismatch(plan, plan->nb_fft, n_bins);
+    if (batch > 65535 || n_frames > 0x7fffffffull) return fail(plan, SGX_INVALID_INPUT, "Invalid input: batch or frame count too large");
     const size_t len = istft_length(plan->p, n_frames);
     if (out_elems != batch * len)
-        return dim_err(plan, batch * len, out_elems);
+        return dim_mismatch(plan, batch * len, out_elems);
     if (!plan->device_ready)
-        return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return fail(plan, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));
+    SGX_TRY_HIP(plan, dg.enter(plan->device));
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const char *route = "";
     sgx_status st;
@@ -1843,36 +1797,36 @@ sgx_status sgx_istft(sgx_plan *plan, const void *stft, size_t batch, size_t n_bi
         if ((st = run_istft(plan, stft, batch, n_frames, out, len, s, &route)) == SGX_OK) plan->istft_route = route;
         return st;
     }
-    if (mem_kind != SGX_MEM_HOST) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
+    if (mem_kind != SGX_MEM_HOST) return fail(plan, SGX_INVALID_INPUT, "Invalid input: unknown mem_kind");
     const size_t in_bytes = batch * n_bins * n_frames * 2 * plan->elem, out_bytes = out_elems * plan->elem;
-    if ((st = grow(plan, &plan->d_in, &plan->d_in_bytes, in_bytes)) != SGX_OK) return st;
-    if ((st = grow(plan, &plan->d_out, &plan->d_out_bytes, out_bytes)) != SGX_OK) return st;
-    SGX_HIP(plan, hipMemcpyAsync(plan->d_in, stft, in_bytes, hipMemcpyHostToDevice, s));
+    if ((st = grow(plan, plan->d_in, in_bytes)) != SGX_OK) return st;
+    if ((st = grow(plan, plan->d_out, out_bytes)) != SGX_OK) return st;
+    SGX_TRY_HIP(plan, hipMemcpyAsync(plan->d_in, stft, in_bytes, hipMemcpyHostToDevice, s));
     if ((st = run_istft(plan, plan->d_in, batch, n_frames, plan->d_out, len, s, &route)) != SGX_OK) return st;
-    SGX_HIP(plan, hipMemcpyAsync(out, plan->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    SGX_TRY_HIP(plan, hipMemcpyAsync(out, plan->d_out, out_bytes, hipMemcpyDeviceToHost, s));
     if ((st = check_flag(plan, s)) == SGX_OK) plan->istft_route = route;  // (synchronises)
     return st;
 }
 
 sgx_status sgx_c2r(sgx_plan *plan, const void *in, size_t in_len, void *out, size_t out_len) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
-    if (!in || !out) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
+    if (plan->kind == K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
+    if (!in || !out) return fail(plan, SGX_INVALID_INPUT, "Invalid input: null buffer");
     const size_t n = plan->p.n_fft, nb = plan->nb_fft;
     if (in_len != nb)  // fft_backend.rs:538-544
-        return dim_err(plan, nb, in_len);
+        return dim_mismatch(plan, nb, in_len);
     if (out_len != n)  // :545-550
-        return dim_err(plan, n, out_len);
+        return dim_mismatch(plan, n, out_len);
     if (!plan->device_ready)
-        return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return fail(plan, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));  // staging, inverse tables, flag: allocated at plan creation
+    SGX_TRY_HIP(plan, dg.enter(plan->device));  // staging, inverse tables, flag: allocated at plan creation
     sgx_status st;
-    SGX_HIP(plan, hipMemcpy(plan->d_in, in, 2 * nb * plan->elem, hipMemcpyHostToDevice));
-    SGX_HIP(plan, hipMemsetAsync(plan->d_flag, 0, sizeof(unsigned), nullptr));
+    SGX_TRY_HIP(plan, hipMemcpy(plan->d_in, in, 2 * nb * plan->elem, hipMemcpyHostToDevice));
+    SGX_TRY_HIP(plan, hipMemsetAsync(plan->d_flag, 0, sizeof(unsigned), nullptr));
     const char *route = "";
     if ((st = launch_c2r_frames(plan, plan->d_in, plan->d_out, 1, 1, false, nullptr, nullptr, &route)) != SGX_OK) return st;
-    SGX_HIP(plan, hipMemcpy(out, plan->d_out, n * plan->elem, hipMemcpyDeviceToHost));
+    SGX_TRY_HIP(plan, hipMemcpy(out, plan->d_out, n * plan->elem, hipMemcpyDeviceToHost));
     if ((st = check_flag(plan, nullptr)) == SGX_OK) plan->istft_route = route;
     return st;
 }
@@ -1888,34 +1842,34 @@ sgx_status sgx_last_dim_mismatch(const sgx_plan *plan, size_t *expected, size_t 
 
 sgx_status sgx_reserve(sgx_plan *plan, size_t batch, size_t n_samples, int32_t host_staging, int32_t inverse) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (batch == 0 || n_samples == 0) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
-    if (inverse && plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
+    if (batch == 0 || n_samples == 0) return fail(plan, SGX_INVALID_INPUT, "Invalid input: samples must be non-empty");
+    if (inverse && plan->kind == K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: a CQT plan has no FFT");
     if (!plan->device_ready)
-        return set_err(plan, SGX_BACKEND, "hip -- FFT backend error: plan has no HIP device (host-only plan)");
+        return fail(plan, SGX_BACKEND, kNoDeviceText);
     DeviceGuard dg;
-    SGX_HIP(plan, dg.enter(plan->device));
+    SGX_TRY_HIP(plan, dg.enter(plan->device));
     const size_t nf = frame_count(plan->p, n_samples);
     const size_t spec_elems = batch * size_t(plan->n_final) * nf * (plan->out_mode == OUT_COMPLEX ? 2 : 1);
     sgx_status st;
     if (plan->p.n_mfcc > 0 &&
-        (st = grow(plan, &plan->d_melbuf, &plan->d_melbuf_bytes, batch * size_t(plan->n_out) * nf * plan->elem)) != SGX_OK)
+        (st = grow(plan, plan->d_melbuf, batch * size_t(plan->n_out) * nf * plan->elem)) != SGX_OK)
         return st;
     if (!inverse && plan->split_bank &&
-        (st = grow(plan, &plan->d_pwbuf, &plan->d_pwbuf_bytes, batch * size_t(plan->nb_fft) * nf * plan->elem)) != SGX_OK)
+        (st = grow(plan, plan->d_pwbuf, batch * size_t(plan->nb_fft) * nf * plan->elem)) != SGX_OK)
         return st;
     if ((plan->kind == K_BIGFFT || (inverse && plan->big.M)) &&
-        (st = grow(plan, &plan->d_big, &plan->d_big_bytes, big_scratch_bytes(plan->big, plan->dtype, batch * ((nf + 1) / 2)))) != SGX_OK)
+        (st = grow(plan, plan->d_big, big_scratch_bytes(plan->big, plan->dtype, batch * ((nf + 1) / 2)))) != SGX_OK)
         return st;
     if (inverse) {  // sgx_istft of `batch` spectra whose frame count is that of n_samples-long signals
         // only the unfused route (rows + overlap-add) touches the frame scratch
         const InverseRoute r = inverse_route(plan, batch, nf, true);
         const bool fused = r.tuned || r.reg;
-        if (!fused && (st = grow(plan, &plan->d_frames, &plan->d_frames_bytes, batch * nf * plan->p.n_fft * plan->elem)) != SGX_OK) return st;
+        if (!fused && (st = grow(plan, plan->d_frames, batch * nf * plan->p.n_fft * plan->elem)) != SGX_OK) return st;
     }
     if (host_staging) {
         const size_t sig_bytes = batch * n_samples * plan->elem, spec_bytes = std::max(spec_elems, batch * size_t(plan->nb_fft) * nf * 2) * plan->elem;
-        if ((st = grow(plan, &plan->d_in, &plan->d_in_bytes, inverse ? spec_bytes : sig_bytes)) != SGX_OK) return st;
-        if ((st = grow(plan, &plan->d_out, &plan->d_out_bytes, inverse ? sig_bytes + batch * plan->p.n_fft * plan->elem : spec_bytes)) != SGX_OK) return st;
+        if ((st = grow(plan, plan->d_in, inverse ? spec_bytes : sig_bytes)) != SGX_OK) return st;
+        if ((st = grow(plan, plan->d_out, inverse ? sig_bytes + batch * plan->p.n_fft * plan->elem : spec_bytes)) != SGX_OK) return st;
     }
     return SGX_OK;
 }
@@ -1928,7 +1882,7 @@ sgx_status sgx_window(const sgx_plan *plan, double *out) {
 
 sgx_status sgx_mel_weights(const sgx_plan *plan, size_t *nnz, uint32_t *row_ptr, uint32_t *cols, double *vals) {
     if (!plan) return SGX_INVALID_INPUT;
-    if (plan->out_mode != OUT_MEL || plan->kind == K_CQT) return set_err(plan, SGX_INVALID_INPUT, "Invalid input: plan has no Mel filterbank");
+    if (plan->out_mode != OUT_MEL || plan->kind == K_CQT) return fail(plan, SGX_INVALID_INPUT, "Invalid input: plan has no Mel filterbank");
     if (nnz) *nnz = plan->mel_col.size();
     if (row_ptr) std::copy(plan->mel_ptr.begin(), plan->mel_ptr.end(), row_ptr);
     if (cols) std::copy(plan->mel_col.begin(), plan->mel_col.end(), cols);

@@ -386,74 +386,3 @@ struct DeviceGuard {
 };
 
 }  // namespace sgx
-
-struct sgx_plan {
-    sgx_params p{};
-    std::vector<double> custom_window;
-    int device = -1;       // -2: host-only plan
-    bool device_ready = false;
-    int dtype = SGX_F32;
-    size_t elem = 4;
-    unsigned nb_fft = 0, n_out = 0;
-    int out_mode = 0, amp = 0;
-    double eps = 0.0;
-    sgx::KernelKind kind = sgx::K_DIRECT_DFT;
-
-    // host tables (f64, as the reference builds them)
-    std::vector<double> window;
-    std::vector<uint32_t> mel_ptr, mel_col;
-    std::vector<double> mel_val;
-    std::vector<double> loghz_freqs;  // LogHz / ERB axis (centre frequencies), empty otherwise
-
-    // device tables
-    void *d_window = nullptr, *d_tw = nullptr, *d_tw1 = nullptr, *d_tw2 = nullptr;
-    void *d_mel_ptr = nullptr, *d_mel_col = nullptr, *d_mel_val = nullptr, *d_mel_pptr = nullptr, *d_mel_pcol = nullptr, *d_mel_pw = nullptr, *d_mm_frag = nullptr, *d_mm_blk = nullptr, *d_mel_sched = nullptr;
-    unsigned mel_sched_words = 0;
-    std::vector<uint32_t> h_mel_sched;  // the tuned kernel's band schedule as built on the host (plan.hip build_band_schedule)
-    unsigned mm_nblk = 0;
-    unsigned mel_pchunks = 0;
-    unsigned mel_contig = 0;
-    void *d_ones = nullptr;  // rectangular window for sgx_r2c
-    // MFCC epilogue: DCT-II basis [n_mfcc][n_mels] and lifter [n_mfcc] in T; Mel-dB scratch (grown on demand)
-    void *d_dct = nullptr, *d_lifter = nullptr, *d_melbuf = nullptr;
-    void *d_mfcc_frag = nullptr;  // fused MFCC epilogue of the tuned f32 kernel: the basis as matrix-core fragments (null: separate launch)
-    unsigned mfcc_frag_words = 0, mfcc_steps = 0, mfcc_mtiles = 0;
-    size_t d_melbuf_bytes = 0;
-    // split filterbank path (long frames): the per-bin power / magnitude tensor between the two launches (grown on demand)
-    void *d_pwbuf = nullptr;
-    size_t d_pwbuf_bytes = 0;
-    bool split_bank = false;  // decided at plan creation (plan.hip)
-    unsigned n_final = 0;  // rows of the final output (n_out, or the MFCC row count)
-    void *d_window_half = nullptr, *d_ones_half = nullptr;  // 0.5*window (exact) for the tuned kernel's real split
-    // inverse path (sgx_istft / sgx_c2r), created on first use: full twiddle table e^{-2 pi i k/n}, frame scratch, flag
-    void *d_itw = nullptr, *d_frames = nullptr, *d_flag = nullptr;
-    void *d_itwr = nullptr, *d_itw1 = nullptr;  // tables of the plan's fused inverse of a single shape, if it has one (plan.hip kFusedInverse)
-    // K_BLUESTEIN: chirp, transformed chirp, length-M twiddles (the sequences themselves never leave LDS: no frame scratch)
-    void *d_bs_chirp = nullptr, *d_bs_tw = nullptr, *d_bs_wc = nullptr, *d_bs_bhp = nullptr;
-    unsigned bs_M = 0;
-    bool bs_fwd_half = false;  // K_BLUESTEIN in half-length complex form (even n_fft whose own convolution does not fit LDS)
-    sgx::BsDevTables bs_half;  // inverse rows of an even n_fft whose own chirp-z does not fit: tables of length n_fft / 2 (inverse_tables)
-    size_t d_frames_bytes = 0;
-    const char *bank_stage = "", *bank_epilogue = "";  // filterbank stage (+ MFCC launch) of the last successful execute (sgx_bank_stage_name): "" before any / without a bank
-    mutable std::string bank_stage_text;               // the two put together for the caller
-    const char *istft_route = "";  // route of the last successful sgx_istft / sgx_c2r (sgx_istft_kernel_name): "" before any
-    // K_BIGFFT: tables of the global-memory transforms and their sequence scratch (grown on demand, pre-sized by sgx_reserve)
-    sgx::BigDev big;
-    unsigned big_n = 0;  // set at creation when the plan's kind is K_BIGFFT (host-only plans have no tables)
-    void *d_big = nullptr;
-    size_t d_big_bytes = 0;
-
-    // K_CQT: kernels as built (f64, packed bin after bin), centre frequencies, the device layout (cqt.hip) and its LDS tiling
-    std::vector<uint32_t> cqt_len;
-    std::vector<double> cqt_re, cqt_im, cqt_freqs;
-    unsigned cqt_groups = 0, cqt_lpad = 0, cqt_m = 0;
-    void *d_cqt_tab = nullptr, *d_cqt_info = nullptr, *d_cqt_len = nullptr;
-
-    // plan-owned staging for host-pointer execution
-    void *d_in = nullptr, *d_out = nullptr;
-    size_t d_in_bytes = 0, d_out_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-
-    mutable std::string err;
-    mutable size_t dm_expected = 0, dm_got = 0;  // the last DimensionMismatch{expected, got} (src/error.rs:19-21)
-};

@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "sgx_internal.h"
+#include "plan_host.h"
 
 using namespace sgx;
 

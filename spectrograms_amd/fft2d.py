@@ -12,20 +12,19 @@ from . import _ffi
 from .params import parse_dtype
 
 
-class Fft2dPlan:
+class Fft2dPlan(_ffi.NativeHandle):
     """One sgx_fft2d (shape + dtype).  Not thread-safe, like the reference's `&mut self` plans."""
+
+    _prefix = "sgx_fft2d"
 
     def __init__(self, nrows: int, ncols: int, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT):
         self._lib = _ffi.lib()
         self.nrows, self.ncols = int(nrows), int(ncols)
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         self._cnp = np.complex64 if self._dt == _ffi.F32 else np.complex128
         h = C.c_void_p()
         st = self._lib.sgx_fft2d_create(self.nrows, self.ncols, self._dt, device, C.byref(h))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_fft2d_last_error(None) or b"").decode())
-        self._h = h
+        self._create(st, h)
         self._device = int(self._lib.sgx_fft2d_device(h))
 
     @property
@@ -51,16 +50,6 @@ class Fft2dPlan:
         if t.dim() != len(shape_tail) + 1 or tuple(t.shape[1:]) != tuple(shape_tail) or t.shape[0] == 0:
             raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected (batch, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}",
                                               tuple(shape_tail), tuple(t.shape[1:]))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_fft2d_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_fft2d_last_error(self._h) or b"").decode())
 
     def _images(self, a) -> np.ndarray:
         x = np.ascontiguousarray(a, dtype=self._np)
@@ -108,7 +97,7 @@ class Fft2dPlan:
     # device-resident batched entry points (torch CUDA tensors), used by the benchmarks
     def forward_torch(self, x, out=None):
         import torch
-        cdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        cdt = self._tdt
         self._device_images(x, "images", (self.nrows, self.ncols), cdt)
         b = x.shape[0]
         if out is None:
@@ -124,7 +113,7 @@ class Fft2dPlan:
     def inverse_torch(self, spec, out=None):
         """ifft2d of [B, nrows, ncols/2+1, 2] half spectra (interleaved re, im) -> [B, nrows, ncols], device resident."""
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         self._device_images(spec, "spectra", (self.nrows, self.ncols // 2 + 1, 2), tdt)
         b = spec.shape[0]
         if out is None:
@@ -142,7 +131,7 @@ class Fft2dPlan:
         k = np.ascontiguousarray(kernel, dtype=self._np)
         if k.ndim != 2:
             raise ValueError("kernel must be 2-D")
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         self._device_images(x, "images", (self.nrows, self.ncols), tdt)
         if out is None:
             out = torch.empty_like(x)
@@ -158,7 +147,7 @@ class Fft2dPlan:
     def filter_torch(self, x, kind: int, lo: float, hi: float = 0.0, out=None):
         """lowpass (0) / highpass (1) / bandpass (2) of [B, nrows, ncols] device images, device resident (src/image_ops.rs:301-430)."""
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         self._device_images(x, "images", (self.nrows, self.ncols), tdt)
         if out is None:
             out = torch.empty_like(x)
@@ -172,9 +161,11 @@ class Fft2dPlan:
         return out
 
 
-class C2cPlan:
+class C2cPlan(_ffi.NativeHandle):
     """1-D complex-to-complex plan: C2cPlan<T> of the reference (src/fft_backend.rs:113-137).  `forward` / `inverse` return a
     new array; neither normalises (the caller divides by n after an inverse)."""
+
+    _prefix = "sgx_c2c"
 
     def __init__(self, n: int, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT):
         self._lib = _ffi.lib()
@@ -183,24 +174,14 @@ class C2cPlan:
         self._cnp = np.complex64 if self._dt == _ffi.F32 else np.complex128
         h = C.c_void_p()
         st = self._lib.sgx_c2c_create(self.n, self._dt, device, C.byref(h))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_c2c_last_error(None) or b"").decode())
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_c2c_destroy(h)
-            self._h = None
+        self._create(st, h)
 
     def _run(self, fn, x) -> np.ndarray:
         buf = np.array(x, dtype=self._cnp, copy=True).ravel()
         st = fn(self._h, buf.ctypes.data, buf.size)
-        if st:
-            msg = (self._lib.sgx_c2c_last_error(self._h) or b"").decode()
-            if st == _ffi.SGX_DIM_MISMATCH:
-                raise _ffi.DimensionMismatchError(msg, self.n, buf.size)
-            raise _ffi._ERR.get(st, _ffi.InternalError)(msg)
+        if st == _ffi.SGX_DIM_MISMATCH:
+            raise _ffi.DimensionMismatchError(self._last_error(self._h), self.n, buf.size)
+        self._check(st)
         return buf
 
     def forward(self, x) -> np.ndarray:
@@ -288,7 +269,7 @@ def gaussian_kernel_2d(size: int, sigma: float, dtype=None) -> np.ndarray:
     total = 0.0
     for v in k.reshape(-1):  # sequential f64 sum, as ndarray's .sum() over the standard layout
         total += float(v)
-    return (k / total).astype(np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64)
+    return (k / total).astype(_ffi.np_dtype(parse_dtype(dtype)))
 
 
 def convolve_fft(image, kernel, dtype=None):
@@ -323,31 +304,31 @@ def sharpen_fft(image, amount: float, dtype=None):
 
 
 def fftshift(arr, dtype=None):
-    return np.fft.fftshift(np.asarray(arr, dtype=np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64))
+    return np.fft.fftshift(np.asarray(arr, dtype=_ffi.np_dtype(parse_dtype(dtype))))
 
 
 def ifftshift(arr, dtype=None):
-    return np.fft.ifftshift(np.asarray(arr, dtype=np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64))
+    return np.fft.ifftshift(np.asarray(arr, dtype=_ffi.np_dtype(parse_dtype(dtype))))
 
 
 def fftshift_1d(arr, dtype=None):
     """1-D fftshift (src/fft2d.rs fftshift_1d): DC to the centre."""
-    a = np.asarray(arr, dtype=np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64)
+    a = np.asarray(arr, dtype=_ffi.np_dtype(parse_dtype(dtype)))
     if a.ndim != 1:
         raise ValueError("fftshift_1d expects a 1-D array")
     return np.fft.fftshift(a)
 
 
 def ifftshift_1d(arr, dtype=None):
-    a = np.asarray(arr, dtype=np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64)
+    a = np.asarray(arr, dtype=_ffi.np_dtype(parse_dtype(dtype)))
     if a.ndim != 1:
         raise ValueError("ifftshift_1d expects a 1-D array")
     return np.fft.ifftshift(a)
 
 
 def fftfreq(n: int, d: float = 1.0, dtype=None):
-    return np.fft.fftfreq(n, d).astype(np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64)
+    return np.fft.fftfreq(n, d).astype(_ffi.np_dtype(parse_dtype(dtype)))
 
 
 def rfftfreq(n: int, d: float = 1.0, dtype=None):
-    return np.fft.rfftfreq(n, d).astype(np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64)
+    return np.fft.rfftfreq(n, d).astype(_ffi.np_dtype(parse_dtype(dtype)))

@@ -17,22 +17,19 @@ from .params import parse_dtype
 _ROUTES = {"auto": _ffi.FIR_ROUTE_AUTO, "generic": _ffi.FIR_ROUTE_GENERIC}
 
 
-def _create_error(st, last_error):
-    return _ffi._ERR.get(st, _ffi.InternalError)((last_error(None) or b"").decode())
-
-
-class FirPlan:
+class FirPlan(_ffi.NativeHandle):
     """One sgx_fir (impulse responses + dtype + device + route).  Not thread-safe, like the reference's `&mut self` convolver.
 
     `ir` is (taps,) — one response for every row — or (rows, taps) — one per row of every call.  `process` is the streaming form
     (n samples in, n out, the last taps - 1 samples kept as the rows' history), `convolve` the full one (n + taps - 1 out, no state).
     """
 
+    _prefix = "sgx_fir"
+
     def __init__(self, ir, block_size: Optional[int] = None, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT,
                  route: str = "auto"):
         self._lib = _ffi.lib()
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         if route not in _ROUTES:
             raise ValueError(f"route must be 'auto' or 'generic', got {route!r}")
         if block_size is not None and int(block_size) <= 0:
@@ -47,20 +44,8 @@ class FirPlan:
         ptr = C.c_void_p()
         st = self._lib.sgx_fir_create(h.ctypes.data_as(C.POINTER(C.c_double)) if h.size else None, taps, rows, self._block or 0,
                                       _ROUTES[route], self._dt, int(device), C.byref(ptr))
-        if st:
-            raise _create_error(st, self._lib.sgx_fir_last_error)
-        self._h = ptr
+        self._create(st, ptr)
         self._device = int(self._lib.sgx_fir_device(ptr))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_fir_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_fir_last_error(self._h) or b"").decode())
 
     taps = property(lambda self: int(self._lib.sgx_fir_taps(self._h)))
     fft_size = property(lambda self: int(self._lib.sgx_fir_fft_size(self._h)), doc="the plan's segment length P")
@@ -105,7 +90,7 @@ class FirPlan:
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
     def _torch(self, x, out, fn, extra):
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         for t, what in ((x, "samples"), (out, "out")):
             if t is None:
                 continue
@@ -151,31 +136,20 @@ class OverlapSaveConvolver(FirPlan):
         return self.process(a)
 
 
-class DeconvPlan:
+class DeconvPlan(_ffi.NativeHandle):
     """One sgx_deconv (lengths + regularization + dtype + device)."""
+
+    _prefix = "sgx_deconv"
 
     def __init__(self, n_len: int, d_len: int, regularization: float = 0.0, dtype: Optional[str] = None,
                  device: int = _ffi.DEVICE_CURRENT):
         self._lib = _ffi.lib()
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         self.n_len, self.d_len = int(n_len), int(d_len)
         ptr = C.c_void_p()
         st = self._lib.sgx_deconv_create(self.n_len, self.d_len, float(regularization), self._dt, int(device), C.byref(ptr))
-        if st:
-            raise _create_error(st, self._lib.sgx_deconv_last_error)
-        self._h = ptr
+        self._create(st, ptr)
         self._device = int(self._lib.sgx_deconv_device(ptr))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_deconv_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_deconv_last_error(self._h) or b"").decode())
 
     output_length = property(lambda self: int(self._lib.sgx_deconv_output_length(self._h)))
     device = property(lambda self: self._device)
@@ -204,7 +178,7 @@ class DeconvPlan:
     def execute_torch(self, numerator, denominator, out=None):
         """(batch, n_len) and (1 or batch, d_len) device tensors -> (batch, output_length), asynchronous on the current stream."""
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         for t, what, w in ((numerator, "numerator", self.n_len), (denominator, "denominator", self.d_len)):
             if not t.is_cuda or t.device.index != self._device:
                 raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
@@ -222,7 +196,7 @@ class DeconvPlan:
 def fft_convolve(a, b, dtype: Optional[str] = None) -> np.ndarray:
     """fft_convolve (src/convolution.rs:25-47): the full linear convolution, length a + b - 1.  `a` is (n,) or (batch, n), `b` (m,) or
     (batch, m); two 1-D operands take the shorter one as the impulse response."""
-    np_dt = np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64
+    np_dt = _ffi.np_dtype(parse_dtype(dtype))
     x, h = np.asarray(a, dtype=np_dt), np.asarray(b, dtype=np_dt)
     if x.ndim == 1 and h.ndim == 1 and x.shape[0] < h.shape[0]:
         x, h = h, x

@@ -18,8 +18,10 @@ from .params import ErbParams, parse_dtype
 N_COEFFS = 11  # SGX_GAMMATONE_COEFFS
 
 
-class GammatonePlan:
+class GammatonePlan(_ffi.NativeHandle):
     """One sgx_gammatone (sample rate, framing, ErbParams, dtype, device).  Not thread-safe, like the other plans."""
+
+    _prefix = "sgx_gammatone"
 
     def __init__(self, sample_rate: float, frame_size: int, hop_size: int, erb_params: ErbParams, dtype: Optional[str] = None,
                  device: int = _ffi.DEVICE_CURRENT):
@@ -33,26 +35,13 @@ class GammatonePlan:
         self._lib = _ffi.lib()
         self.sample_rate, self.frame_size, self.hop_size, self.erb_params = float(sample_rate), fs, hs, erb_params
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         floor = erb_params.db_floor
         h = C.c_void_p()
         st = self._lib.sgx_gammatone_create(self.sample_rate, fs, hs, erb_params.n_filters, erb_params.f_min, erb_params.f_max,
                                             1 if erb_params.spacing == "apple_tr35" else 0, int(floor is not None),
                                             0.0 if floor is None else float(floor), self._dt, int(device), C.byref(h))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_gammatone_last_error(None) or b"").decode())
-        self._h = h
+        self._create(st, h)
         self._device = int(self._lib.sgx_gammatone_device(h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_gammatone_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_gammatone_last_error(self._h) or b"").decode())
 
     @property
     def device(self) -> int:
@@ -116,7 +105,7 @@ class GammatonePlan:
         """(batch, n) device tensor (unit stride along n, any row stride >= n) -> (batch, n_bands, n_frames), asynchronous on the
         current stream."""
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         if not x.is_cuda or x.device.index != self._device:
             raise ValueError(f"samples is on {x.device}, the plan is bound to cuda:{self._device}")
         if x.dtype != tdt or x.dim() != 2 or x.shape[0] == 0:

@@ -68,14 +68,15 @@ def _check_window_size(ws: int) -> None:
         raise _ffi.InvalidInputError(f"Invalid input: window_size must be >= 4, got {ws}")
 
 
-class MdctPlan:
+class MdctPlan(_ffi.NativeHandle):
     """One sgx_mdct (params + dtype + device).  Not thread-safe, like the reference's `&mut self` plans."""
+
+    _prefix = "sgx_mdct"
 
     def __init__(self, params: MdctParams, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT):
         self._lib = _ffi.lib()
         self.params = params
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         w = params.window
         cw, clen = None, 0
         if w.kind == _ffi.WIN_CUSTOM:
@@ -84,20 +85,8 @@ class MdctPlan:
         h = C.c_void_p()
         st = self._lib.sgx_mdct_create(params.window_size, params.hop_size, w.kind, w.param, cw, clen, self._dt, int(device),
                                        C.byref(h))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_mdct_last_error(None) or b"").decode())
-        self._h = h
+        self._create(st, h)
         self._device = int(self._lib.sgx_mdct_device(h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_mdct_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_mdct_last_error(self._h) or b"").decode())
 
     @property
     def device(self) -> int:
@@ -171,7 +160,7 @@ class MdctPlan:
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
     def _tensor(self, t, what: str, ndim: int):
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         if not t.is_cuda or t.device.index != self._device:
             raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
         if t.dtype != tdt or not t.is_contiguous():

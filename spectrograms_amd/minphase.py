@@ -18,18 +18,19 @@ _ROUTES = {"auto": _ffi.MINPHASE_ROUTE_AUTO, "generic": _ffi.MINPHASE_ROUTE_GENE
 DEFAULT_OVERSAMPLE = 8  # src/min_phase.rs:33
 
 
-class MinPhasePlan:
+class MinPhasePlan(_ffi.NativeHandle):
     """One sgx_minphase (taps + output length + oversampling + dtype + device + route).  Not thread-safe.
 
     Every row of a call is one impulse response of `taps` samples; its minimum-phase equivalent comes out truncated to
     `output_length` = min(out_len, fft_size) samples (out_len None: taps).
     """
 
+    _prefix = "sgx_minphase"
+
     def __init__(self, taps: int, out_len: Optional[int] = None, oversample: int = DEFAULT_OVERSAMPLE, dtype: Optional[str] = None,
                  device: int = _ffi.DEVICE_CURRENT, route: str = "auto"):
         self._lib = _ffi.lib()
         self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         if route not in _ROUTES:
             raise ValueError(f"route must be 'auto' or 'generic', got {route!r}")
         taps, oversample = int(taps), int(oversample)
@@ -38,20 +39,8 @@ class MinPhasePlan:
             raise ValueError("taps, out_len and oversample must not be negative")  # usize
         ptr = C.c_void_p()
         st = self._lib.sgx_minphase_create(taps, out_len, oversample, _ROUTES[route], self._dt, int(device), C.byref(ptr))
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_minphase_last_error(None) or b"").decode())
-        self._h = ptr
+        self._create(st, ptr)
         self._device = int(self._lib.sgx_minphase_device(ptr))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.sgx_minphase_destroy(h)
-            self._h = None
-
-    def _check(self, st):
-        if st:
-            raise _ffi._ERR.get(st, _ffi.InternalError)((self._lib.sgx_minphase_last_error(self._h) or b"").decode())
 
     taps = property(lambda self: int(self._lib.sgx_minphase_taps(self._h)))
     fft_size = property(lambda self: int(self._lib.sgx_minphase_fft_size(self._h)), doc="n = next_power_of_two(taps * max(oversample, 1))")
@@ -81,7 +70,7 @@ class MinPhasePlan:
     def execute_torch(self, ir, out=None):
         """(batch, taps) device tensor -> (batch, output_length), asynchronous on the current stream.  `out` must not overlap `ir`."""
         import torch
-        tdt = torch.float32 if self._dt == _ffi.F32 else torch.float64
+        tdt = self._tdt
         for t, what in ((ir, "ir"), (out, "out")):
             if t is None:
                 continue
@@ -106,7 +95,7 @@ class MinPhasePlan:
 def minimum_phase_with(ir, out_len: int, oversample: int, dtype: Optional[str] = None) -> np.ndarray:
     """minimum_phase_with (src/min_phase.rs:67-141): `ir` is (taps,) or (batch, taps); the first min(out_len, fft_size) samples of the
     minimum-phase response of every row, fft_size = next_power_of_two(taps * max(oversample, 1))."""
-    np_dt = np.float32 if parse_dtype(dtype) == _ffi.F32 else np.float64
+    np_dt = _ffi.np_dtype(parse_dtype(dtype))
     h = np.asarray(ir, dtype=np_dt)
     if h.ndim not in (1, 2):
         raise ValueError("ir must be 1-D (taps,) or 2-D (batch, taps)")
