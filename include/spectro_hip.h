@@ -154,6 +154,30 @@ typedef struct {
  * sgx_axes (frequencies f_k), sgx_reserve (forward) and sgx_shard_execute work as on a Mel plan; the FFT entry points (sgx_r2c,
  * sgx_c2r, sgx_istft) and sgx_mel_weights return SGX_INVALID_INPUT. */
 sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out);
+/* ---- constant-Q transform: cqt() / CqtResult (src/cqt.rs:517-709), the complex coefficients on cqt()'s own framing.
+ * For a signal of n samples cqt() takes klen = min(n, 16384) (:664), builds CqtKernel::generate(params, sr, klen) (:316-376: the
+ * kernels of sgx_plan_create_cqt with n_fft = klen, except that the loop stops at the first bin with f_k >= sr / 2, :333-335, so
+ * n_bins counts the bins below Nyquist) and applies them to the frames [f hop, f hop + klen), f < (n - klen) / hop + 1 (:671-675):
+ * no centring, and hop > klen is legal.  Y_k of a frame is the sum of sgx_plan_create_cqt with n_fft = klen (:481-514).
+ *   Read from params: n_fft (= klen, 1 .. 16384), hop_size (1 .. 2^24, not bound by n_fft), sample_rate_hz, amp_scale, dtype,
+ *   device, has_log_params / floor_db; centre must be 0 and freq_scale SGX_FREQ_CQT.  amp_scale: SGX_AMP_COMPLEX gives Y itself,
+ *   [batch][n_bins][n_frames] interleaved (re, im) in T as the complex STFT (CqtResult::data); POWER / MAGNITUDE / DECIBELS give
+ *   re re + im im, its sqrt (CqtResult::to_power / to_magnitude, :591-612, each product and sum rounded in T) or its dB with the floor.
+ *   Checks: those of sgx_plan_create_cqt less three — complex output, f_{n_bins-1} >= sr / 2 (the bins from the first such one on
+ *   are dropped; SGX_INVALID_INPUT "no CQT bin lies below the Nyquist frequency" if none is left, where the reference is undefined)
+ *   and hop_size <= n_fft.
+ * The plan is a CQT plan: sgx_execute, sgx_execute_timed, sgx_output_shape, sgx_axes (the kept f_k; times f hop / sr), sgx_reserve,
+ * sgx_cqt_kernels (the kept bins) and sgx_kernel_name serve it.  A caller who executes with n_samples < n_fft gets the STFT's one
+ * zero-padded frame (sgx_output_shape), which is NOT cqt() of that signal: cqt() of a signal shorter than 16384 samples needs a
+ * plan with n_fft = n_samples.
+ * Calls whose signals hold one frame each (n_samples < n_fft + hop_size) run tiles of 16 signals ("cqt_mfma_rows") instead of one
+ * tile per signal from a batch of 4096 on (measured: below that the per-signal tiles are faster until they run out of CUs); both
+ * give the same bits.  sgx_kernel_name reports the route of the last call on such a plan. */
+sgx_status sgx_plan_create_cqt_transform(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out);
+/* Test entry: route = 0 automatic (above), 1 = per-signal tiles always, 2 = the rows tiles for every one-frame call (calls with
+ * more frames keep the frame tiles).  SGX_INVALID_INPUT on any plan that is not a CQT transform
+ * plan.  Reads no environment variable. */
+sgx_status sgx_cqt_set_route(sgx_plan *plan, int32_t route);
 /* The kernels as built (f64, before the cast to T), packed bin after bin: bin k's L_k values start at sum_{i<k} L_i.  Pass NULL
  * arrays to query `total` (= sum L_k) only; `lengths` has n_bins entries.  Works on host-only plans. */
 sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im);

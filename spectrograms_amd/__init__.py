@@ -9,6 +9,7 @@ from ._ffi import DimensionMismatchError, FFTBackendError, InternalError, Invali
 from .binaural import (BinauralPlan, ILDSpectrogramParams, ILRSpectrogramParams, IPDSpectrogramParams, ITDSpectrogramParams,
                        IldSpectrogram, IlrSpectrogram, IpdSpectrogram, ItdSpectrogram, compute_ild_spectrogram, compute_ilr_spectrogram,
                        compute_ilr_spectrogram_diff, compute_ipd_spectrogram, compute_itd_spectrogram, compute_itd_spectrogram_diff)
+from .cqt import CqtResult, CqtTransformPlan, cqt
 from .fft2d import (C2cPlan, Fft2dPlan, Fft2dPlanner, bandpass_filter, convolve_fft, detect_edges_fft, fft2d, fftfreq, fftshift,
                     fftshift_1d, gaussian_kernel_2d, highpass_filter, ifft2d, ifftshift, ifftshift_1d, lowpass_filter,
                     magnitude_spectrum_2d, power_spectrum_2d, rfftfreq, sharpen_fft)
@@ -27,6 +28,7 @@ from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .minphase import MinPhasePlan, minimum_phase, minimum_phase_with
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
+from .source import ChromaSource, CqtSource, GammatoneSource, MfccSource
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
 
 # The reference exposes one plan class per (frequency scale, amplitude scale) (python/spectrograms/__init__.pyi:1087-1245);
@@ -61,4 +63,5 @@ __all__ = [
     "GammatonePlan", "gammatone_iir_spectrogram", "gammatone_center_frequencies",
     "FirPlan", "OverlapSaveConvolver", "DeconvPlan", "fft_convolve", "fft_deconvolve",
     "MinPhasePlan", "minimum_phase", "minimum_phase_with",
+    "cqt", "CqtResult", "CqtTransformPlan", "GammatoneSource", "CqtSource", "ChromaSource", "MfccSource",
 ]

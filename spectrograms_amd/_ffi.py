@@ -35,7 +35,7 @@ SYMBOLS = [
     "sgx_reserve", "sgx_plan_device", "sgx_last_dim_mismatch",
     "sgx_c2c_create", "sgx_c2c_destroy", "sgx_c2c_forward", "sgx_c2c_inverse", "sgx_c2c_last_error",
     "sgx_comm_unique_id", "sgx_comm_create", "sgx_comm_adopt", "sgx_comm_destroy", "sgx_comm_last_error", "sgx_gather", "sgx_shard_execute", "sgx_shard_execute_chunked",
-    "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels",
+    "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels", "sgx_plan_create_cqt_transform", "sgx_cqt_set_route",
     "sgx_mdct_create", "sgx_mdct_destroy", "sgx_mdct_output_shape", "sgx_mdct_inverse_length", "sgx_mdct_forward", "sgx_mdct_inverse",
     "sgx_mdct_reserve", "sgx_mdct_window", "sgx_mdct_kernel_name", "sgx_mdct_device", "sgx_mdct_last_error",
     "sgx_binaural_create", "sgx_binaural_destroy", "sgx_binaural_output_shape", "sgx_binaural_axes", "sgx_binaural_execute",
@@ -188,6 +188,8 @@ def lib() -> C.CDLL:
     L.sgx_clock_probe.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
     L.sgx_clock_probe.restype = C.c_int32
     L.sgx_plan_create_cqt.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
+    L.sgx_plan_create_cqt_transform.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
+    L.sgx_cqt_set_route.argtypes = [vp, C.c_int32]
     L.sgx_cqt_kernels.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgx_mdct_create.argtypes = [sz, sz, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.sgx_mdct_destroy.argtypes = [vp]

@@ -12,7 +12,11 @@
 //   M A fragments (16 frames each, from LDS) into M accumulators of v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 — both a k-ordered
 //   fma chain in T.  LDS = false reads the A operands from global memory (spans too large for LDS: long hops, f64 long kernels).
 //   Epilogue: Re / Im meet across the lane pair (2c, 2c + 1), |Y|^2 = re re + im im in T (Complex::norm_sqr), then the amplitude
-//   scale, stored [b][bin][frame].
+//   scale, stored [b][bin][frame].  CPLX = true (the transform plans' complex output, cqt() of src/cqt.rs:656-709) stores (re, im)
+//   itself, one complex value per store.
+//   ROWS = true (transform plans, one frame per signal): the 16 M rows of a tile are 16 M consecutive signals instead of 16 M frames of
+//   one signal — the A row pitch is the sample stride and the A operands come from global memory.  Each output is the same k-ordered
+//   fma chain over the same taps as on the per-signal tiles, so the two routes give the same bits.
 //
 // Non-finite samples.  Inside a group a shorter bin has zero weights in front of its own L_k taps; 0 x NaN = NaN would let a NaN /
 // Inf that the reference never multiplies for that bin poison it.  The span copy marks every frame that has a non-finite sample
@@ -35,6 +39,7 @@ struct Mf;
 template <>
 struct Mf<float> {
     typedef float V4 __attribute__((ext_vector_type(4)));
+    typedef float V2 __attribute__((ext_vector_type(2)));
     static __device__ __forceinline__ V4 mfma(float a, float b, V4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
     // C/D: lane l, register e holds row 4 (l >> 4) + e, column l & 15
     static __device__ __forceinline__ unsigned row(unsigned l, unsigned e) { return 4u * (l >> 4) + e; }
@@ -42,6 +47,7 @@ struct Mf<float> {
 template <>
 struct Mf<double> {
     typedef double V4 __attribute__((ext_vector_type(4)));
+    typedef double V2 __attribute__((ext_vector_type(2)));
     static __device__ __forceinline__ V4 mfma(double a, double b, V4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
     // the f64 form does not use the f32 map (cdna_hip_programming.md §3): row (l >> 4) + 4 e, column l & 15
     static __device__ __forceinline__ unsigned row(unsigned l, unsigned e) { return (l >> 4) + 4u * e; }
@@ -72,15 +78,29 @@ __device__ __forceinline__ T sample_at(const T *xb, long long s, unsigned long l
     return (s >= 0 && (unsigned long long)s < n) ? xb[s] : T(0);
 }
 
-template <typename T, int M, bool LDS>
+// one output value: (re, im) as one store of 2 T (rows are only 2 T aligned), or the amplitude of |Y|^2
+template <typename T, bool CPLX>
+__device__ __forceinline__ void put_bin(T *out, size_t at, T re, T im, int amp, T eps) {
+    if (CPLX) {
+        typedef typename Mf<T>::V2 V2;
+        reinterpret_cast<V2 *>(out)[at] = V2{re, im};
+    } else {
+        const T pw = add_rn(mul_rn(re, re), mul_rn(im, im));
+        out[at] = amp_t(pw, amp, eps);
+    }
+}
+
+template <typename T, int M, bool LDS, bool CPLX, bool ROWS>
 __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
+    static_assert(!(ROWS && LDS), "the spans of 16 M signals do not fit LDS");
     typedef typename Mf<T>::V4 V4;
     constexpr unsigned F = 16u * M;
     extern __shared__ unsigned char smem[];
     __shared__ unsigned long long s_bad;  // frames of the tile with a non-finite sample in reach (bit r: frame f0 + r)
     T *span_lds = reinterpret_cast<T *>(smem);
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const unsigned b = blockIdx.x / a.tiles, f0 = (blockIdx.x % a.tiles) * F;
+    // ROWS: b is the tile's first signal and every row is frame 0 of signal b + row
+    const unsigned b = ROWS ? blockIdx.x * F : blockIdx.x / a.tiles, f0 = ROWS ? 0u : (blockIdx.x % a.tiles) * F;
     const T *xb = static_cast<const T *>(a.x) + (size_t)b * a.sample_stride;
     const unsigned hop = a.hop, lpad = a.lpad;
     const unsigned skew = (hop % 8u == 0u) ? 1u : 0u;
@@ -89,7 +109,15 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
     const unsigned span = (F - 1u) * hop + lpad;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    for (unsigned p = tid; p < span; p += 256u) {
+    if (ROWS) {  // per row: that signal's [n_fft - lpad, n_fft) reach
+        for (unsigned p = tid; p < F * lpad; p += 256u) {
+            const unsigned r = p / lpad;
+            if ((unsigned long long)b + r >= a.batch) break;
+            const T v = sample_at(xb + (size_t)r * a.sample_stride, s0 + (long long)(p - r * lpad), a.n_samples);
+            if (!finite_t(v)) atomicOr(&s_bad, 1ull << r);
+        }
+    }
+    for (unsigned p = tid; !ROWS && p < span; p += 256u) {
         const T v = sample_at(xb, s0 + (long long)p, a.n_samples);
         if (LDS) span_lds[p + (skew ? p / hop : 0u)] = v;
         if (!finite_t(v)) {  // frames r with r hop <= p < r hop + lpad
@@ -121,6 +149,15 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
         if (skew) { q = t / hop; rem = t - q * hop; }
         unsigned addr = rr * row_pitch + t + q;  // LDS word of (frame rr, tap t)
         long long gaddr = s0 + (long long)rr * hop + t;  // signal index of the same (global A path)
+        if (ROWS) gaddr = s0 + (long long)t;
+        const T *xrow[M];  // ROWS: the signals of this lane's A rows (rr + 16 i), null past the batch
+        if (ROWS) {
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                const unsigned long long sig = (unsigned long long)b + rr + 16u * (unsigned)i;
+                xrow[i] = sig < a.batch ? xb + (size_t)(rr + 16u * (unsigned)i) * a.sample_stride : nullptr;
+            }
+        }
         V4 acc[M];
 #pragma unroll
         for (int i = 0; i < M; ++i) acc[i] = V4{0, 0, 0, 0};
@@ -141,6 +178,7 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
                 for (int i = 0; i < M; ++i) {
                     T av;
                     if (LDS) av = span_lds[addr + (unsigned)i * 16u * row_pitch];
+                    else if (ROWS) av = xrow[i] ? sample_at(xrow[i], gaddr, a.n_samples) : T(0);
                     else av = sample_at(xb, gaddr + (long long)i * 16 * hop, a.n_samples);
                     acc[i] = Mf<T>::mfma(av, bc[u], acc[i]);
                 }
@@ -162,12 +200,12 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
                 const T v = acc[i][e];
                 const T w = __shfl_xor(v, 1);
                 const T re = odd ? w : v, im = odd ? v : w;
-                const unsigned fr = 16u * i + Mf<T>::row(lane, e), frame = f0 + fr;
+                const unsigned fr = 16u * i + Mf<T>::row(lane, e), frame = ROWS ? 0u : f0 + fr;
+                const bool live = ROWS ? (unsigned long long)b + fr < a.batch : frame < a.n_frames;
                 // the pair splits the stores: the Re lane takes registers 0, 1, the Im lane 2, 3
-                if ((e >> 1) == (odd ? 1u : 0u) && bin < a.n_bins && frame < a.n_frames && !((bad >> fr) & 1ull)) {
-                    const T pw = add_rn(mul_rn(re, re), mul_rn(im, im));
-                    out[((size_t)b * a.n_bins + bin) * a.n_frames + frame] = amp_t(pw, a.amp, eps);
-                }
+                if ((e >> 1) == (odd ? 1u : 0u) && bin < a.n_bins && live && !((bad >> fr) & 1ull))
+                    put_bin<T, CPLX>(out, ((size_t)b * a.n_bins + (ROWS ? (size_t)fr * a.n_bins : 0) + bin) * a.n_frames + frame, re, im,
+                                     a.amp, eps);
             }
         }
     }
@@ -175,8 +213,9 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
     // exact recompute of the frames with a non-finite sample in reach (rare: a wave-uniform skip otherwise)
     if (bad) {
         for (unsigned fr = 0; fr < F; ++fr) {
-            const unsigned frame = f0 + fr;
-            if (!((bad >> fr) & 1ull) || frame >= a.n_frames) continue;
+            const unsigned frame = ROWS ? 0u : f0 + fr;
+            if (!((bad >> fr) & 1ull) || frame >= a.n_frames) continue;  // (ROWS: only rows inside the batch are ever marked)
+            const T *xs = ROWS ? xb + (size_t)fr * a.sample_stride : xb;
             for (unsigned k = tid; k < a.n_bins; k += 256u) {
                 const unsigned g = k >> 3, c = k & 7u;
                 const unsigned off = info[4u * g], Lg = info[4u * g + 1u], Lk = a.len[k];
@@ -185,17 +224,19 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
                 const long long sb = (long long)frame * hop - (long long)a.pad + (long long)a.n_fft - (long long)Lg;
                 T re = T(0), im = T(0);
                 for (unsigned jr = Lg - Lk; jr < Lg; ++jr) {
-                    const T xv = sample_at(xb, sb + (long long)jr, a.n_samples);
+                    const T xv = sample_at(xs, sb + (long long)jr, a.n_samples);
                     re = add_rn(re, mul_rn(col[(size_t)jr * 16u], xv));
                     im = add_rn(im, mul_rn(col[(size_t)jr * 16u + 1u], xv));
                 }
-                const T pw = add_rn(mul_rn(re, re), mul_rn(im, im));
-                out[((size_t)b * a.n_bins + k) * a.n_frames + frame] = amp_t(pw, a.amp, eps);
+                put_bin<T, CPLX>(out, ((size_t)b * a.n_bins + (ROWS ? (size_t)fr * a.n_bins : 0) + k) * a.n_frames + frame, re, im, a.amp, eps);
             }
         }
     }
 }
 
+// Rows route: 16 signals per workgroup.  A wider tile would reuse each B fragment for more rows, but it also divides the number of
+// workgroups, and at 16 signals a batch of 4096 is one workgroup per CU; the group blocks it re-reads stay in L2.
+constexpr int kCqtRowsM = 1;
 constexpr size_t kCqtLdsMax = 160u * 1024u - 64u;  // dynamic LDS of one workgroup (s_bad is static)
 #ifndef SGX_CQT_LDS_PREF
 #define SGX_CQT_LDS_PREF (80u * 1024u - 64u)  // spans up to this size leave room for two workgroups per CU
@@ -207,27 +248,28 @@ size_t cqt_lds_bytes(unsigned m, unsigned hop, unsigned lpad, size_t elem) {
     return words * elem;
 }
 
-template <typename T, int M, bool LDS>
+template <typename T, int M, bool LDS, bool CPLX, bool ROWS>
 hipError_t launch_t(const CqtArgs &a, hipStream_t s) {
     const size_t lds = LDS ? cqt_lds_bytes(M, a.hop, a.lpad, sizeof(T)) : 0;
     if (lds > 64u * 1024u) {
-        const hipError_t e = set_max_dynamic_lds((const void *)k_cqt<T, M, LDS>, (int)kCqtLdsMax);
+        const hipError_t e = set_max_dynamic_lds((const void *)k_cqt<T, M, LDS, CPLX, ROWS>, (int)kCqtLdsMax);
         if (e != hipSuccess) return e;
     }
-    const unsigned long long blocks = (unsigned long long)a.batch * a.tiles;
+    const unsigned long long blocks = ROWS ? ((unsigned long long)a.batch + 16u * M - 1u) / (16u * M) : (unsigned long long)a.batch * a.tiles;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7fffffffull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL((k_cqt<T, M, LDS>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((k_cqt<T, M, LDS, CPLX, ROWS>), dim3((unsigned)blocks), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_dt(const CqtArgs &a, unsigned m, hipStream_t s) {
+template <typename T, bool CPLX>
+hipError_t launch_dt(const CqtArgs &a, unsigned m, bool rows, hipStream_t s) {
+    if (rows) return launch_t<T, kCqtRowsM, false, CPLX, true>(a, s);
     switch (m) {
-    case 4: return launch_t<T, 4, true>(a, s);
-    case 2: return launch_t<T, 2, true>(a, s);
-    case 1: return launch_t<T, 1, true>(a, s);
-    default: return launch_t<T, 4, false>(a, s);
+    case 4: return launch_t<T, 4, true, CPLX, false>(a, s);
+    case 2: return launch_t<T, 2, true, CPLX, false>(a, s);
+    case 1: return launch_t<T, 1, true, CPLX, false>(a, s);
+    default: return launch_t<T, 4, false, CPLX, false>(a, s);
     }
 }
 
@@ -241,11 +283,13 @@ unsigned cqt_lds_m(unsigned hop, unsigned lpad, int dtype) {
     return 0;
 }
 
-hipError_t launch_cqt(const CqtArgs &a0, unsigned lds_m, int dtype, hipStream_t s) {
+hipError_t launch_cqt(const CqtArgs &a0, unsigned lds_m, int dtype, bool cplx, bool rows, hipStream_t s) {
     CqtArgs a = a0;
     const unsigned F = 16u * (lds_m ? lds_m : 4u);
     a.tiles = (a.n_frames + F - 1u) / F;
-    return dtype == SGX_F64 ? launch_dt<double>(a, lds_m, s) : launch_dt<float>(a, lds_m, s);
+    if (rows && a.n_frames != 1u) return hipErrorInvalidValue;  // (a row of the rows route is one signal's only frame)
+    if (dtype == SGX_F64) return cplx ? launch_dt<double, true>(a, lds_m, rows, s) : launch_dt<double, false>(a, lds_m, rows, s);
+    return cplx ? launch_dt<float, true>(a, lds_m, rows, s) : launch_dt<float, false>(a, lds_m, rows, s);
 }
 
 }  // namespace sgx

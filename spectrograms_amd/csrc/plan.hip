@@ -343,7 +343,9 @@ size_t frame_count(const sgx_params &p, size_t n_samples) {  // StftPlan::frame_
 
 // ---- constant-Q kernels (CqtKernel::generate, src/cqt.rs:317-436), f64 -------------------------------------------------------
 // CqtParams::new / with_q_factor (:17-70, :112-165) and FrequencyMapping<Cqt>::new (src/spectrogram.rs:1785-1806)
-sgx_status cqt_validate(const sgx_params &p, const sgx_cqt_params &c, std::string &msg) {
+// transform: sgx_plan_create_cqt_transform (cqt(), src/cqt.rs:656-709) — complex output is its own, and bins at or above Nyquist are
+// dropped by build_cqt_kernels instead of refused (CqtKernel::generate :333-335)
+sgx_status cqt_validate(const sgx_params &p, const sgx_cqt_params &c, std::string &msg, bool transform = false) {
     auto bad = [&](const char *m) { msg = std::string("Invalid input: ") + m; return SGX_INVALID_INPUT; };
     if (c.bins_per_octave == 0) return bad("bins_per_octave must be > 0");
     if (c.n_octaves == 0) return bad("n_octaves must be > 0");
@@ -353,16 +355,17 @@ sgx_status cqt_validate(const sgx_params &p, const sgx_cqt_params &c, std::strin
     if (c.window_kind < SGX_WIN_RECTANGULAR || c.window_kind > SGX_WIN_CUSTOM) return bad("unknown window type");
     // make_window panics on a Custom window whose length is not the kernel's (src/spectrogram.rs:2219-2226): the L_k differ per bin
     if (c.window_kind == SGX_WIN_CUSTOM) return bad("CQT kernels need a window of every kernel length: a custom window is not accepted");
-    if (p.amp_scale == SGX_AMP_COMPLEX) return bad("complex output is not available on a CQT plan");
+    if (p.amp_scale == SGX_AMP_COMPLEX && !transform) return bad("complex output is not available on a CQT plan");
     if (p.n_mfcc > 0) return bad("MFCC requires a Mel / Decibels plan");
     const unsigned nb = c.bins_per_octave * c.n_octaves;
     const double f_max = c.f_min * std::exp2(double(nb - 1) / double(c.bins_per_octave));
-    if (f_max >= p.sample_rate_hz / 2.0) return bad("CQT maximum frequency must be below Nyquist frequency");
+    if (f_max >= p.sample_rate_hz / 2.0 && !transform) return bad("CQT maximum frequency must be below Nyquist frequency");
     return SGX_OK;
 }
 
+// below_nyquist: keep the bins in front of the first one with f_k >= sr / 2 only (CqtKernel::generate :333-335; possibly none)
 void build_cqt_kernels(const sgx_params &p, const sgx_cqt_params &c, std::vector<uint32_t> &len, std::vector<double> &re,
-                       std::vector<double> &im, std::vector<double> &freqs) {
+                       std::vector<double> &im, std::vector<double> &freqs, bool below_nyquist = false) {
     const unsigned nb = c.bins_per_octave * c.n_octaves;
     const double sr = p.sample_rate_hz;
     len.assign(nb, 0);
@@ -375,6 +378,11 @@ void build_cqt_kernels(const sgx_params &p, const sgx_cqt_params &c, std::vector
     std::vector<double> w;
     for (unsigned k = 0; k < nb; ++k) {
         const double f = c.f_min * std::exp2(double(k) / double(c.bins_per_octave));  // bin_frequency :143-146
+        if (below_nyquist && f >= sr / 2.0) {
+            len.resize(k);
+            freqs.resize(k);
+            break;
+        }
         size_t L = sat_usize(std::round(c.q_factor * sr / f));  // f64::round: half away from zero; `as usize` saturates
         L = std::min<size_t>(std::max<size_t>(L, 1), p.n_fft);
         wp.n_fft = unsigned(L);
@@ -1050,6 +1058,13 @@ sgx_status run_timed(sgx_plan *pl, hipStream_t s, int iters, float *ms, F launch
     return SGX_OK;
 }
 
+// Batch from which a one-frame call of a transform plan takes the rows route by itself.  Measured (profiles/time_cqt_transform.txt,
+// signals of 8000 samples, CqtParams(12, 6, 55.0), complex): both routes are bound by one workgroup's serial tap chain, 116 - 125 us
+// on the per-signal tiles (LDS) against 241 - 282 us on the rows tiles (global A) for every batch from 16 to 256, so below the
+// point where the per-signal tiles run out of CUs the rows route loses 2 x; at 4096 it wins 2.8 x (f32 333 against 918 us) and
+// 3.1 x (f64 387 against 1205 us).  Nothing between 256 and 4096 was measured, so those batches keep the per-signal tiles.
+constexpr size_t kCqtRowsMinBatch = 4096;
+
 sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out, size_t n_frames,
                    hipStream_t s, int iters, float *ms) {
     CqtArgs a{};
@@ -1070,10 +1085,16 @@ sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, 
     a.len = static_cast<const unsigned *>(pl->d_cqt_len);
     a.amp = pl->amp;
     a.eps = pl->eps;
-    return run_timed(pl, s, iters, ms, [&]() -> sgx_status {
-        SGX_TRY_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, s));
+    // One frame per signal (a transform plan fed signals shorter than n_fft + hop), large batches: tiles of 16 signals instead of
+    // one tile per signal with a single live row (DESIGN.md "Constant-Q transform").  Same bits either way.
+    const bool cplx = pl->out_mode == OUT_COMPLEX;
+    const bool rows = pl->cqt_transform && n_frames == 1 && (pl->cqt_route == 2 || (pl->cqt_route == 0 && batch >= kCqtRowsMinBatch));
+    const sgx_status st = run_timed(pl, s, iters, ms, [&]() -> sgx_status {
+        SGX_TRY_HIP(pl, launch_cqt(a, pl->cqt_m, pl->dtype, cplx, rows, s));
         return SGX_OK;
     });
+    if (st == SGX_OK) pl->cqt_rows_last = rows;
+    return st;
 }
 
 sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out,
@@ -1467,7 +1488,7 @@ const char *sgx_kernel_name(const sgx_plan *plan) {
     case K_REG_RADIX: return "reg_radix";
     case K_BLUESTEIN: return "bluestein";
     case K_BIGFFT: return plan->big_n & (plan->big_n - 1) ? "big_chirpz" : "big_four_step";
-    case K_CQT: return plan->cqt_m ? "cqt_mfma_lds" : "cqt_mfma_global";
+    case K_CQT: return plan->cqt_rows_last ? "cqt_mfma_rows" : plan->cqt_m ? "cqt_mfma_lds" : "cqt_mfma_global";
     default: return "direct_dft";
     }
 }
@@ -1641,6 +1662,51 @@ sgx_status sgx_plan_create_cqt(const sgx_params *params, const sgx_cqt_params *c
     pl->cqt_lpad = (*std::max_element(pl->cqt_len.begin(), pl->cqt_len.end()) + 15u) & ~15u;
     pl->cqt_m = cqt_lds_m(params->hop_size, pl->cqt_lpad, pl->dtype);
     return open_plan(pl, out, [](sgx_plan *pl) { return pl->dtype == SGX_F64 ? cqt_device_tables<double>(pl) : cqt_device_tables<float>(pl); });
+}
+
+// cqt() (src/cqt.rs:656-709): frames of n_fft = min(n, 16384) samples from sample 0, no centring, any hop; the bins below Nyquist
+sgx_status sgx_plan_create_cqt_transform(const sgx_params *params, const sgx_cqt_params *cqt, sgx_plan **out) {
+    if (out) *out = nullptr;
+    if (!params || !cqt || !out) return create_fail(SGX_INVALID_INPUT, "Invalid input: null argument");
+    if (params->freq_scale != SGX_FREQ_CQT)
+        return create_fail(SGX_INVALID_INPUT, "Invalid input: sgx_plan_create_cqt_transform requires freq_scale = SGX_FREQ_CQT");
+    if (params->centre) return create_fail(SGX_INVALID_INPUT, "Invalid input: a CQT transform plan frames the signal from sample 0 (centre must be 0)");
+    if (params->n_fft > 16384u)
+        return create_fail(SGX_INVALID_INPUT, "Invalid input: a CQT transform frame (n_fft) is at most 16384 samples");  // :664
+    // cqt() has no hop_size <= n_fft rule; the tiles address a span of up to 63 hops in 32 bits
+    if (params->hop_size > (1u << 24)) return create_fail(SGX_INVALID_INPUT, "Invalid input: hop_size must be <= 2^24 on a CQT transform plan");
+    std::string msg;
+    sgx_params v = *params;  // the sgx_params checks, less the two that do not apply here
+    v.hop_size = std::min(v.hop_size, v.n_fft);
+    if (v.amp_scale == SGX_AMP_COMPLEX) v.amp_scale = SGX_AMP_POWER;
+    sgx_status st = validate(v, msg);
+    if (st != SGX_OK) return create_fail(st, msg);
+    if ((st = cqt_validate(*params, *cqt, msg, true)) != SGX_OK) return create_fail(st, msg);
+    sgx_plan *pl = new_plan(*params);
+    if (!pl) return create_fail(SGX_INTERNAL, "Internal error: out of memory");
+    pl->kind = K_CQT;
+    pl->cqt_transform = true;
+    pl->out_mode = params->amp_scale == SGX_AMP_COMPLEX ? OUT_COMPLEX : OUT_MEL;
+    build_cqt_kernels(pl->p, *cqt, pl->cqt_len, pl->cqt_re, pl->cqt_im, pl->cqt_freqs, true);
+    if (pl->cqt_len.empty()) {  // (the reference builds an empty kernel set unchecked here)
+        delete pl;
+        return create_fail(SGX_INVALID_INPUT, "Invalid input: no CQT bin lies below the Nyquist frequency");
+    }
+    pl->n_out = pl->n_final = unsigned(pl->cqt_len.size());
+    pl->p.n_mels = pl->n_out;
+    pl->cqt_groups = (pl->n_out + 7) / 8;
+    pl->cqt_lpad = (*std::max_element(pl->cqt_len.begin(), pl->cqt_len.end()) + 15u) & ~15u;
+    pl->cqt_m = cqt_lds_m(params->hop_size, pl->cqt_lpad, pl->dtype);
+    return open_plan(pl, out, [](sgx_plan *pl) { return pl->dtype == SGX_F64 ? cqt_device_tables<double>(pl) : cqt_device_tables<float>(pl); });
+}
+
+sgx_status sgx_cqt_set_route(sgx_plan *plan, int32_t route) {
+    if (!plan) return SGX_INVALID_INPUT;
+    if (plan->kind != K_CQT || !plan->cqt_transform) return fail(plan, SGX_INVALID_INPUT, "Invalid input: plan is not a CQT transform plan");
+    if (route < 0 || route > 2)
+        return fail(plan, SGX_INVALID_INPUT, "Invalid input: route must be 0 (automatic), 1 (per-signal tiles) or 2 (rows tiles)");
+    plan->cqt_route = route;
+    return SGX_OK;
 }
 
 sgx_status sgx_cqt_kernels(const sgx_plan *plan, size_t *total, uint32_t *lengths, double *re, double *im) {

@@ -90,6 +90,10 @@ struct sgx_plan {
     std::vector<double> cqt_re, cqt_im, cqt_freqs;
     unsigned cqt_groups = 0, cqt_lpad = 0, cqt_m = 0;
     void *d_cqt_tab = nullptr, *d_cqt_info = nullptr, *d_cqt_len = nullptr;
+    // transform plans (sgx_plan_create_cqt_transform): cqt()'s framing and bin rule; one-frame calls take the rows route unless
+    // sgx_cqt_set_route asked for the per-signal tiles; sgx_kernel_name reports the route of the last call
+    bool cqt_transform = false, cqt_rows_last = false;
+    int cqt_route = 0;
 
     // plan-owned staging for host-pointer execution
     sgx::DevBuf d_in, d_out;

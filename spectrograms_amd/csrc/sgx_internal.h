@@ -293,7 +293,7 @@ hipError_t launch_big_c2c(const BigDev &t, const C2cArgs &c, void *scratch, int 
 constexpr unsigned kCqtWaves = 4;
 struct CqtArgs {
     const void *x;
-    void *out;  // [batch][n_bins][n_frames] T
+    void *out;  // [batch][n_bins][n_frames] T, or (re, im) pairs of T (the transform plans' complex output)
     unsigned long long sample_stride, n_samples;
     unsigned batch, n_fft, hop, pad, n_frames, n_bins, n_groups;
     unsigned lpad;   // L_0 rounded up to 16: a frame's taps [n_fft - lpad, n_fft) are the only ones ever read
@@ -306,7 +306,9 @@ struct CqtArgs {
 };
 // frames per wave-row tile multiple m (4, 2, 1) whose sample span fits LDS, 0: none does (the A operands come from global memory)
 unsigned cqt_lds_m(unsigned hop, unsigned lpad, int dtype);
-hipError_t launch_cqt(const CqtArgs &a, unsigned lds_m, int dtype, hipStream_t s);
+// cplx: store Y itself (interleaved re, im) instead of the amplitude of |Y|^2.  rows: the rows route (n_frames must be 1): a tile's
+// rows are consecutive signals, A operands from global memory; the same bits as the per-signal tiles.
+hipError_t launch_cqt(const CqtArgs &a, unsigned lds_m, int dtype, bool cplx, bool rows, hipStream_t s);
 
 // make_window (src/spectrogram.rs:2159-2235) in f64 at length p.n_fft for p.window_kind / p.window_param (plan.hip build_window);
 // SGX_WIN_CUSTOM copies `custom`.  The MDCT plans (mdct.hip) build their analysis / synthesis window with it.

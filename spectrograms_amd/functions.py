@@ -58,14 +58,16 @@ def Plan(params, amp, mapping, db, dtype, mfcc=None, inverse=False):
 
 
 def clear_fft_plan_cache() -> None:
-    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct, the binaural and the gammatone plans included."""
+    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct, the binaural, the gammatone and the cqt() plans included."""
     from .binaural import clear_binaural_plan_cache
+    from .cqt import clear_cqt_plan_cache
     from .gammatone import clear_gammatone_plan_cache
     from .mdct import clear_mdct_plan_cache
     _PLAN_CACHE.clear()
     clear_mdct_plan_cache()
     clear_binaural_plan_cache()
     clear_gammatone_plan_cache()
+    clear_cqt_plan_cache()
 
 
 def fft_plan_cache_info():

@@ -176,17 +176,25 @@ class Mfcc:
         return self._data.__dlpack_device__()
 
 
+def signal_length(samples) -> int:
+    """Samples per signal of an (n,) or (batch, n) array or tensor; empty input is the reference's NonEmptySlice error."""
+    shape = tuple(samples.shape) if hasattr(samples, "shape") else np.shape(samples)
+    if len(shape) not in (1, 2):
+        raise ValueError("samples must be 1-D (n,) or 2-D (batch, n)")
+    if 0 in shape:
+        raise _ffi.InvalidInputError("Invalid input: samples must be non-empty")
+    return int(shape[-1])
+
+
 class Plan:
     """One sgx_plan.  Not thread-safe (mirrors `&mut self`; reference plan classes are `unsendable`)."""
 
     def __init__(self, params: SpectrogramParams, amp: int, mel: Optional[MelParams] = None,
                  db: Optional[LogParams] = None, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT,
                  mfcc: Optional[MfccParams] = None):
-        self._lib = _ffi.lib()
         self._params, self._mel, self._db = params, mel, db
-        self._dt = parse_dtype(dtype)
-        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
         self._amp = amp
+        self._sample_rate, self._hop = params.sample_rate, params.stft.hop_size
         st = params.stft
         p = _ffi.SgxParams()
         p.n_fft, p.hop_size, p.centre = st.n_fft, st.hop_size, int(st.centre)
@@ -220,17 +228,24 @@ class Plan:
         p.amp_scale = amp
         p.has_log_params = int(db is not None)
         p.floor_db = db.floor_db if db is not None else 0.0
-        p.dtype, p.device = self._dt, device
         self._mfcc = mfcc
         if mfcc is not None:
             p.n_mfcc, p.mfcc_include_c0, p.mfcc_lifter = mfcc.n_mfcc, int(mfcc.include_c0), mfcc.lifter
-        h = C.c_void_p()
         if cq is not None:
-            _ffi.raise_status(self._lib.sgx_plan_create_cqt(C.byref(p), C.byref(cq), C.byref(h)))
+            self._open(p, dtype, device, lambda L, pp, h: L.sgx_plan_create_cqt(pp, C.byref(cq), h))
         else:
-            _ffi.raise_status(self._lib.sgx_plan_create(C.byref(p), C.byref(h)))
-        self._h = h
+            self._open(p, dtype, device, lambda L, pp, h: L.sgx_plan_create(pp, h))
         self.n_fft = st.n_fft
+
+    def _open(self, p, dtype, device, create) -> None:
+        """Create the sgx_plan of `p` in `dtype` on `device` with the C entry `create(lib, params, handle)`."""
+        self._lib = _ffi.lib()
+        self._dt = parse_dtype(dtype)
+        self._np = np.float32 if self._dt == _ffi.F32 else np.float64
+        p.dtype, p.device = self._dt, device
+        h = C.c_void_p()
+        _ffi.raise_status(create(self._lib, C.byref(p), C.byref(h)))
+        self._h = h
         self._device = int(self._lib.sgx_plan_device(h))  # resolved ordinal (DEVICE_CURRENT was bound at creation); -2: host only
         self._frame_plan = None  # no-centre sibling for compute_frame, created on first use
 
@@ -314,7 +329,7 @@ class Plan:
         L_k holding K_k[j] = w[j] e^(+i 2 pi f_k j / sr) after the sparsity step and the normalisation."""
         total = C.c_size_t()
         _ffi.raise_status(self._lib.sgx_cqt_kernels(self._h, C.byref(total), None, None, None), self._h)
-        lens = np.empty(self._mel.num_bins, np.uint32)
+        lens = np.empty(self.output_shape(self.n_fft)[0], np.uint32)  # (a transform plan keeps the bins below Nyquist only)
         re, im = np.empty(total.value, np.float64), np.empty(total.value, np.float64)
         _ffi.raise_status(self._lib.sgx_cqt_kernels(self._h, None, lens.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                     re.ctypes.data_as(C.POINTER(C.c_double)),
@@ -408,6 +423,31 @@ class Plan:
         if isinstance(self._mel, ChromaParams):
             return Chromagram(data, self._mel)
         return Spectrogram(data, freqs, times, self._params, self._db.floor_db if self._db else None)
+
+    # ---- SpectrogramSource (src/source.rs:66-93): every spectrogram plan is a source of [n_bands x n_frames] matrices
+    @property
+    def n_bands(self) -> int:
+        return self.output_shape(self.n_fft)[0]
+
+    def center_frequencies(self) -> list:
+        """The plan's frequency axis, low to high (freq_axis().frequencies())."""
+        return self.axes(0)[0].tolist()
+
+    @property
+    def sample_rate(self) -> float:
+        return self._sample_rate
+
+    @property
+    def hop_seconds(self) -> float:
+        return self._hop / self._sample_rate  # frame_period_seconds
+
+    def compute_matrix(self, samples):
+        """(n,) samples -> the (n_bands, n_frames) matrix of `compute(samples)`; (batch, n) -> (batch, n_bands, n_frames), NumPy or a
+        torch tensor on the plan's device as `compute_batch` takes them."""
+        signal_length(samples)
+        if not hasattr(samples, "shape"):
+            samples = np.asarray(samples)
+        return self.compute_batch(samples) if len(samples.shape) == 2 else self.compute_batch(samples[None])[0]
 
     def compute_frame(self, samples, frame_idx: int) -> np.ndarray:
         """SpectrogramPlan::compute_frame (:335-372): one column, computed from the n_fft-sample span it covers.  The reference
