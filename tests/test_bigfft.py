@@ -144,8 +144,10 @@ def test_gpu_long_frames_filterbank_and_many_sequences():
     assert lin.kernel_name == "big_chirpz"
     P = lin.compute_batch(big).cpu().numpy()
     refp = orc.spectrogram_batch(orc.Params(n_fft=n_fft, hop=hop), x[:, :30000])
-    for r in (0, 5, 599, 1199):
-        assert np.max(np.abs(P[r] - refp[r % 4])) < 1e-10 * max(1.0, refp.max())
+    assert P.shape == (1200,) + refp.shape[1:]
+    # every row (a signal holds 6 sequences; chunks of 512 end inside signals 85, 170, ...: rows on both sides of every seam)
+    worst = np.max(np.abs(P.reshape((300, 4) + refp.shape[1:]) - refp[None]), axis=(2, 3)).reshape(1200)
+    assert (worst < 1e-10 * max(1.0, refp.max())).all(), int(np.argmax(worst))
 
 
 @pytest.mark.gpu
