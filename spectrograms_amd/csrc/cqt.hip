@@ -55,11 +55,39 @@ struct Mf<double> {
 
 __device__ __forceinline__ bool finite_t(float v) { return __builtin_isfinite(v); }
 __device__ __forceinline__ bool finite_t(double v) { return __builtin_isfinite(v); }
-// the reference's `acc += T::from_f64(c) * x` and `re * re + im * im` are separate roundings (rustc never contracts)
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
+// the reference's `acc += T::from_f64(c) * x` and `re * re + im * im` are separate roundings (rustc never contracts).  __fmul_rn /
+// __dmul_rn / __fadd_rn / __dadd_rn are plain `*` and `+` in the HIP headers, which hipcc's default -ffp-contract=fast-honor-pragmas
+// fuses (it did in every f64 instance: v_mul_f64 + v_fmac_f64); only the pragma keeps the two roundings apart.
+template <typename T>
+__device__ __forceinline__ T mul_rn(T a, T b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+template <typename T>
+__device__ __forceinline__ T add_rn(T a, T b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// f64 only: hold every consumer of the accumulators back until the last v_mfma_f64_16x16x4_f64 of a 16-tap step has retired.  The
+// instruction takes 16 passes on gfx950; the wait states hipcc puts in front of the v_accvgpr_read of its result (11) are those of
+// an 8-pass instruction.  In the M = 1 instances the accumulator goes through VGPRs once per step, and without the LDS skew nothing
+// else stands between the 4th MFMA and that read: the last register written, the high word of element 3 (frame rows 12 .. 15), was
+// read before the MFMA wrote it, so those rows lost every 4th MFMA (tests/test_cqt_readback.py, hop 441 f64).  64 wait states on
+// top of the compiler's own are what the whole suite ran with (13 % at the f64 bench shape); 32 passed the read-back as well, and
+// 16, one per pass, should suffice but has not run.
+#define SGX_CQT_DRAIN_ASM "s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
+template <int M>
+__device__ __forceinline__ void mfma_drain(Mf<float>::V4 (&)[M]) {}
+template <int M>
+__device__ __forceinline__ void mfma_drain(Mf<double>::V4 (&acc)[M]) {
+    static_assert(M == 1 || M == 2 || M == 4, "one operand list per tile multiple");
+    if constexpr (M == 1) asm volatile(SGX_CQT_DRAIN_ASM : "+a"(acc[0]));
+    if constexpr (M == 2) asm volatile(SGX_CQT_DRAIN_ASM : "+a"(acc[0]), "+a"(acc[1]));
+    if constexpr (M == 4) asm volatile(SGX_CQT_DRAIN_ASM : "+a"(acc[0]), "+a"(acc[1]), "+a"(acc[2]), "+a"(acc[3]));
+}
+#undef SGX_CQT_DRAIN_ASM
+
 // amplitude scale of a power value (src/spectrogram.rs:1986-2080): sqrt, or 10 log10(max(p, eps)) — max ignores a NaN power like
 // f32::max / f64::max; f32 dB through the hardware log2 as the other kernels, f64 through db_f64.h
 __device__ __forceinline__ float amp_t(float p, int amp, float eps) {
@@ -189,6 +217,7 @@ __global__ __launch_bounds__(256) void k_cqt(CqtArgs a) {
                     if (rem >= hop) { rem -= hop; addr += 1u; }
                 }
             }
+            mfma_drain<M>(acc);
         }
         // epilogue: column rr = 2 c + (0: Re, 1: Im) of bin bin0 + c; lanes rr and rr ^ 1 hold the two parts of the same rows
         const unsigned bin = bin0 + (rr >> 1);
