@@ -32,18 +32,18 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
  *    on one plan that go to different streams must be ordered by the caller (events), as must a host-pointer call behind a
  *    device-pointer call still in flight.  A call does not depend on the calls before it: a larger, smaller, failed, host- or
  *    device-pointer call in between changes neither the bits nor the route of the next one (the DC / Nyquist flag word is
- *    cleared per call; the one exception is the state a streaming FIR plan exists to carry: sgx_fir_process reads and replaces
- *    the plan's history, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
+ *    cleared per call; the one exception is the state a streaming plan exists to carry: sgx_fir_process reads and replaces
+ *    the plan's history, sgx_stream_push the stream's pending samples, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
- *    by tests/test_stream_order.py.
+ *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py).
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H
@@ -586,6 +586,59 @@ size_t sgx_minphase_taps(const sgx_minphase *plan);
 const char *sgx_minphase_kernel_name(const sgx_minphase *plan); /* "k_minphase" or "minphase_generic" */
 int32_t sgx_minphase_device(const sgx_minphase *plan);
 const char *sgx_minphase_last_error(const sgx_minphase *plan); /* NULL plan: the text of the last failed create */
+
+/* ---- streaming spectrogram plans: the batched form of the SpectrogramPlan::compute_frame loop (src/spectrogram.rs:335-372,
+ * python/examples/streaming.py) for signals that arrive in blocks.  A stream runs any plan sgx_plan_create accepts (every mapping,
+ * amplitude scale, MFCC, window and both types; SGX_FREQ_CQT is SGX_INVALID_INPUT) on `batch` rows in lock step: every row gets the
+ * same number of new samples in a call, and that number may change from call to call.  It carries the rows' pending samples on the
+ * device; a call returns the frames that became complete, [batch][n_bins][f] T (complex: interleaved pairs, out_elems counts T).
+ * Let pad = centre ? n_fft / 2 : 0.  The stream holds a pending run of p virtual samples per row, the same p for every row.
+ *   after creation or sgx_stream_reset   p = pad (zeros), frames_emitted = 0, the row count is free
+ *   sgx_stream_push of C >= 1 samples    P = p + C;  f = P >= n_fft ? (P - n_fft) / hop_size + 1 : 0;  the frames start at pending
+ *                                        offsets 0, hop, .., (f - 1) hop;  afterwards p = P - f hop (0 <= p < n_fft).  f = 0 is legal:
+ *                                        the block is staged, `out` is not touched (it may be NULL) and out_elems must be 0.
+ *   sgx_stream_flush                     appends pad zeros and emits the frames that then fit.  A stream that has taken samples but
+ *                                        emitted no frame since its reset (centre = 0 and fewer than n_fft samples in total) emits the
+ *                                        reference's single zero-filled frame (frame_count :1239-1242); one that has taken no sample
+ *                                        emits nothing.  Then the stream stands as after a reset, except that its row count stays fixed.
+ * After the flush the frames of all calls, laid end to end, are the frames of sgx_execute of the same sgx_params on the whole signals:
+ * the same count, the same order, equal to rounding.  Bit equality across different cuts of a signal is NOT promised: the frame count
+ * of a call decides the launch shape, which may pick another variant of the transform.  The staging itself is exact: a push returns
+ * the bits of the no-centre plan on the rows (pending | block).
+ * The first push after creation or reset fixes the row count; a later push with another batch is SGX_DIM_MISMATCH (expected / got in
+ * the text, as sgx_fir_process).  n_samples = 0 is SGX_INVALID_INPUT ("samples must be non-empty"); a wrong out_elems is
+ * SGX_DIM_MISMATCH with the two numbers in sgx_stream_last_error.
+ * A call is two launches: k_stream_stage (the pending samples and the new block into the second of two stream-owned work buffers, 16-byte
+ * stores) and the plan's own launch on that buffer; sgx_stream_kernel_name is the sgx_kernel_name of the plan that runs the frames.
+ * mem_kind as sgx_execute: SGX_MEM_HOST uses stream-owned staging and is synchronous, SGX_MEM_DEVICE is asynchronous on `stream` (a
+ * hipStream_t) and is one operation of that stream; the stream's buffers are used in call order only, so calls that go to different
+ * hipStreams must be ordered by the caller.  sgx_stream_reserve sizes the work buffers, the plan's scratch and (host_staging) the
+ * staging for pushes of up to max_block samples on `batch` rows and the flush behind them: such calls allocate nothing and do not
+ * synchronise; a larger one replaces a work buffer once (it waits for `stream` and the device).  It needs a stream without pending
+ * samples of earlier pushes (after creation, reset or flush).  device -1: the current device, -2: a host-only stream (validation and
+ * the bookkeeping below; push, flush and reserve return SGX_BACKEND). */
+typedef struct sgx_stream sgx_stream; /* opaque; same single-caller rule as sgx_fir */
+sgx_status sgx_stream_create(const sgx_params *params, sgx_stream **out);
+void sgx_stream_destroy(sgx_stream *s);
+/* Pure bookkeeping (host-only streams too): one push of n_samples onto `pending` gives n_frames and leaves pending_after. */
+sgx_status sgx_stream_step(const sgx_stream *s, size_t pending, size_t n_samples, size_t *n_frames, size_t *pending_after);
+size_t sgx_stream_pending(const sgx_stream *s);        /* p */
+size_t sgx_stream_frames_emitted(const sgx_stream *s); /* since creation / reset / flush */
+sgx_status sgx_stream_flush_frames(const sgx_stream *s, size_t *n_frames); /* what sgx_stream_flush would emit now */
+size_t sgx_stream_n_bins(const sgx_stream *s);
+/* row r at x + r * sample_stride (elements of T, sample_stride >= n_samples); out_elems = batch * n_bins * f (* 2 for complex) */
+sgx_status sgx_stream_push(sgx_stream *s, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out, size_t out_elems,
+                           int32_t mem_kind, void *stream);
+sgx_status sgx_stream_flush(sgx_stream *s, void *out, size_t out_elems, int32_t mem_kind, void *stream);
+/* The zeros after a reset are not read from memory, so nothing is enqueued on `stream`. */
+sgx_status sgx_stream_reset(sgx_stream *s, void *stream);
+sgx_status sgx_stream_reserve(sgx_stream *s, size_t batch, size_t max_block, int32_t host_staging);
+/* A diagnostic: how many times the stream has allocated or replaced one of its own buffers (work buffers, host staging) so far.  It
+ * does not move across calls that fit what was reserved. */
+size_t sgx_stream_allocations(const sgx_stream *s);
+const char *sgx_stream_kernel_name(const sgx_stream *s);
+int32_t sgx_stream_device(const sgx_stream *s);
+const char *sgx_stream_last_error(const sgx_stream *s); /* NULL: the text of the last failed create */
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,9 @@ SYMBOLS = [
     "sgx_deconv_device", "sgx_deconv_last_error",
     "sgx_minphase_create", "sgx_minphase_destroy", "sgx_minphase_execute", "sgx_minphase_reserve", "sgx_minphase_fft_size",
     "sgx_minphase_output_length", "sgx_minphase_taps", "sgx_minphase_kernel_name", "sgx_minphase_device", "sgx_minphase_last_error",
+    "sgx_stream_create", "sgx_stream_destroy", "sgx_stream_step", "sgx_stream_pending", "sgx_stream_frames_emitted", "sgx_stream_flush_frames",
+    "sgx_stream_n_bins", "sgx_stream_push", "sgx_stream_flush", "sgx_stream_reset", "sgx_stream_reserve", "sgx_stream_allocations",
+    "sgx_stream_kernel_name", "sgx_stream_device", "sgx_stream_last_error",
 ]
 
 
@@ -274,6 +277,24 @@ def lib() -> C.CDLL:
     L.sgx_minphase_device.restype = C.c_int32
     L.sgx_minphase_last_error.argtypes = [vp]
     L.sgx_minphase_last_error.restype = C.c_char_p
+    L.sgx_stream_create.argtypes = [C.POINTER(SgxParams), C.POINTER(vp)]
+    L.sgx_stream_destroy.argtypes = [vp]
+    L.sgx_stream_destroy.restype = None
+    L.sgx_stream_step.argtypes = [vp, sz, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.sgx_stream_flush_frames.argtypes = [vp, C.POINTER(sz)]
+    for f in (L.sgx_stream_pending, L.sgx_stream_frames_emitted, L.sgx_stream_n_bins, L.sgx_stream_allocations):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_stream_push.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_stream_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
+    L.sgx_stream_reset.argtypes = [vp, vp]
+    L.sgx_stream_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_stream_kernel_name.argtypes = [vp]
+    L.sgx_stream_kernel_name.restype = C.c_char_p
+    L.sgx_stream_device.argtypes = [vp]
+    L.sgx_stream_device.restype = C.c_int32
+    L.sgx_stream_last_error.argtypes = [vp]
+    L.sgx_stream_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -186,6 +186,48 @@ def signal_length(samples) -> int:
     return int(shape[-1])
 
 
+def flatten_params(params: SpectrogramParams, amp: int, mel=None, db: Optional[LogParams] = None, mfcc: Optional[MfccParams] = None):
+    """The sgx_params of a plan's Python arguments (dtype and device are the caller's to fill in).  Returns it with the array its
+    custom_window pointer refers to (None without one: the caller keeps it alive across the create call) and, for a CqtParams
+    mapping, the sgx_cqt_params that travel beside it (else None)."""
+    st = params.stft
+    p = _ffi.SgxParams()
+    p.n_fft, p.hop_size, p.centre = st.n_fft, st.hop_size, int(st.centre)
+    p.window_kind, p.window_param = st.window.kind, st.window.param
+    cw = None
+    if st.window.kind == _ffi.WIN_CUSTOM:
+        cw = np.ascontiguousarray(st.window.coefficients, np.float64)
+        p.custom_window = cw.ctypes.data_as(C.POINTER(C.c_double))
+        p.custom_window_len = cw.size
+    p.sample_rate_hz = params.sample_rate
+    cq = None
+    if isinstance(mel, CqtParams):  # sgx_plan_create_cqt: the mapping's own parameters travel in sgx_cqt_params
+        p.freq_scale = _ffi.FREQ_CQT
+        cq = _ffi.SgxCqtParams(mel.bins_per_octave, mel.n_octaves, mel.f_min, mel.q_factor, mel.window.kind, mel.window.param,
+                               mel.sparsity_threshold, int(mel.normalize))
+    elif isinstance(mel, ChromaParams):
+        p.freq_scale = _ffi.FREQ_CHROMA
+        p.f_min, p.f_max, p.chroma_tuning, p.chroma_norm = mel.f_min, mel.f_max, mel.tuning, mel.norm.code
+    elif isinstance(mel, ErbParams):
+        p.freq_scale = _ffi.FREQ_ERB
+        p.n_mels, p.f_min, p.f_max = mel.n_filters, mel.f_min, mel.f_max
+        p.erb_spacing = 1 if mel.spacing == "apple_tr35" else 0
+    elif isinstance(mel, LogHzParams):
+        p.freq_scale = _ffi.FREQ_LOGHZ
+        p.n_mels, p.f_min, p.f_max = mel.n_bins, mel.f_min, mel.f_max
+    elif mel is not None:
+        p.freq_scale = _ffi.FREQ_MEL
+        p.n_mels, p.f_min, p.f_max, p.mel_norm = mel.n_mels, mel.f_min, mel.f_max, mel.norm.code
+    else:
+        p.freq_scale = _ffi.FREQ_LINEAR
+    p.amp_scale = amp
+    p.has_log_params = int(db is not None)
+    p.floor_db = db.floor_db if db is not None else 0.0
+    if mfcc is not None:
+        p.n_mfcc, p.mfcc_include_c0, p.mfcc_lifter = mfcc.n_mfcc, int(mfcc.include_c0), mfcc.lifter
+    return p, cw, cq
+
+
 class Plan:
     """One sgx_plan.  Not thread-safe (mirrors `&mut self`; reference plan classes are `unsendable`)."""
 
@@ -195,47 +237,13 @@ class Plan:
         self._params, self._mel, self._db = params, mel, db
         self._amp = amp
         self._sample_rate, self._hop = params.sample_rate, params.stft.hop_size
-        st = params.stft
-        p = _ffi.SgxParams()
-        p.n_fft, p.hop_size, p.centre = st.n_fft, st.hop_size, int(st.centre)
-        p.window_kind, p.window_param = st.window.kind, st.window.param
-        self._cw = None
-        if st.window.kind == _ffi.WIN_CUSTOM:
-            self._cw = np.ascontiguousarray(st.window.coefficients, np.float64)
-            p.custom_window = self._cw.ctypes.data_as(C.POINTER(C.c_double))
-            p.custom_window_len = self._cw.size
-        p.sample_rate_hz = params.sample_rate
-        cq = None
-        if isinstance(mel, CqtParams):  # sgx_plan_create_cqt: the mapping's own parameters travel in sgx_cqt_params
-            p.freq_scale = _ffi.FREQ_CQT
-            cq = _ffi.SgxCqtParams(mel.bins_per_octave, mel.n_octaves, mel.f_min, mel.q_factor, mel.window.kind, mel.window.param,
-                                   mel.sparsity_threshold, int(mel.normalize))
-        elif isinstance(mel, ChromaParams):
-            p.freq_scale = _ffi.FREQ_CHROMA
-            p.f_min, p.f_max, p.chroma_tuning, p.chroma_norm = mel.f_min, mel.f_max, mel.tuning, mel.norm.code
-        elif isinstance(mel, ErbParams):
-            p.freq_scale = _ffi.FREQ_ERB
-            p.n_mels, p.f_min, p.f_max = mel.n_filters, mel.f_min, mel.f_max
-            p.erb_spacing = 1 if mel.spacing == "apple_tr35" else 0
-        elif isinstance(mel, LogHzParams):
-            p.freq_scale = _ffi.FREQ_LOGHZ
-            p.n_mels, p.f_min, p.f_max = mel.n_bins, mel.f_min, mel.f_max
-        elif mel is not None:
-            p.freq_scale = _ffi.FREQ_MEL
-            p.n_mels, p.f_min, p.f_max, p.mel_norm = mel.n_mels, mel.f_min, mel.f_max, mel.norm.code
-        else:
-            p.freq_scale = _ffi.FREQ_LINEAR
-        p.amp_scale = amp
-        p.has_log_params = int(db is not None)
-        p.floor_db = db.floor_db if db is not None else 0.0
         self._mfcc = mfcc
-        if mfcc is not None:
-            p.n_mfcc, p.mfcc_include_c0, p.mfcc_lifter = mfcc.n_mfcc, int(mfcc.include_c0), mfcc.lifter
+        p, self._cw, cq = flatten_params(params, amp, mel, db, mfcc)
         if cq is not None:
             self._open(p, dtype, device, lambda L, pp, h: L.sgx_plan_create_cqt(pp, C.byref(cq), h))
         else:
             self._open(p, dtype, device, lambda L, pp, h: L.sgx_plan_create(pp, h))
-        self.n_fft = st.n_fft
+        self.n_fft = params.stft.n_fft
 
     def _open(self, p, dtype, device, create) -> None:
         """Create the sgx_plan of `p` in `dtype` on `device` with the C entry `create(lib, params, handle)`."""
@@ -466,6 +474,11 @@ class Plan:
             sib = self._frame_plan = Plan(SpectrogramParams(type(st)(st.n_fft, st.hop_size, st.window, False), self._params.sample_rate),
                                           self._amp, self._mel, self._db, self.dtype, self._device, self._mfcc)
         return sib.compute_batch(seg[None, :])[0][:, 0]
+
+    def stream(self):
+        """A `StreamingPlan` with this plan's parameters, dtype and device: the same frames from signals that arrive in blocks."""
+        from .streaming import StreamingPlan
+        return StreamingPlan(self._params, self._amp, self._mel, self._db, self.dtype, self._device, self._mfcc)
 
     def r2c(self, frame) -> np.ndarray:
         """Conforming R2cPlan::process (src/fft_backend.rs:423-431) on one frame of n_fft reals."""

@@ -1,0 +1,167 @@
+"""Streaming spectrogram plans over the sgx_stream_* C ABI: signals that arrive in blocks.
+
+`StreamingPlan` takes the arguments of `Plan` and runs the same frames: `push(block)` hands `(B, C)` new samples to `B` rows that run
+in lock step (any `C` per call) and returns the frames that became complete, `flush()` the ones the trailing padding completes.
+After the flush the frames of all calls, laid end to end, are those of `Plan.compute_batch` on the whole signals: the same count in
+the same order, equal to rounding (not bit for bit across different cuts: the frame count of a call decides the launch shape).  The
+rows' pending samples stay on the device between calls; the first push after creation or `reset()` fixes `B`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _ffi
+from .params import LogParams, MfccParams, SpectrogramParams, parse_dtype
+from .planner import flatten_params
+
+
+class StreamingPlan(_ffi.NativeHandle):
+    """One sgx_stream (a plan's parameters + dtype + device + the rows' pending samples).  Not thread-safe, like `Plan`."""
+
+    _prefix = "sgx_stream"
+
+    def __init__(self, params: SpectrogramParams, amp: int, mel=None, db: Optional[LogParams] = None, dtype: Optional[str] = None,
+                 device: int = _ffi.DEVICE_CURRENT, mfcc: Optional[MfccParams] = None):
+        self._lib = _ffi.lib()
+        self._dt = parse_dtype(dtype)
+        self._complex = amp == _ffi.AMP_COMPLEX
+        self._hop, self._sample_rate = params.stft.hop_size, params.sample_rate
+        p, cw, _ = flatten_params(params, amp, mel, db, mfcc)  # (cw: the custom window stays alive across the create call)
+        p.dtype, p.device = self._dt, int(device)
+        ptr = C.c_void_p()
+        self._create(self._lib.sgx_stream_create(C.byref(p), C.byref(ptr)), ptr)
+        self._device = int(self._lib.sgx_stream_device(ptr))
+        self._rows = 0          # fixed by the first push; reset() frees it
+        self._squeeze = False   # the pushes are 1-D: the frames come back without the batch axis
+        self._torch = None      # the device of the last pushed tensor (None: NumPy pushes)
+
+    pending = property(lambda self: int(self._lib.sgx_stream_pending(self._h)), doc="virtual samples held back per row")
+    frames_emitted = property(lambda self: int(self._lib.sgx_stream_frames_emitted(self._h)), doc="frames since creation / reset / flush")
+    n_bins = property(lambda self: int(self._lib.sgx_stream_n_bins(self._h)))
+    kernel_name = property(lambda self: self._lib.sgx_stream_kernel_name(self._h).decode(), doc="kernel_name of the plan that runs the frames")
+    allocations = property(lambda self: int(self._lib.sgx_stream_allocations(self._h)),
+                           doc="how often the stream has allocated or replaced one of its own buffers (it stands still within what reserve() sized)")
+    device = property(lambda self: self._device)
+    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
+    is_complex = property(lambda self: self._complex)
+
+    def frames(self, n_samples: int) -> int:
+        """Frames a push of `n_samples` samples per row would return now."""
+        f, after = C.c_size_t(), C.c_size_t()
+        self._check(self._lib.sgx_stream_step(self._h, self.pending, int(n_samples), C.byref(f), C.byref(after)))
+        return f.value
+
+    def flush_frames(self) -> int:
+        """Frames `flush()` would return now."""
+        f = C.c_size_t()
+        self._check(self._lib.sgx_stream_flush_frames(self._h, C.byref(f)))
+        return f.value
+
+    def times(self, f: int) -> np.ndarray:
+        """Time axis (seconds) of the next `f` frames: (frames_emitted + i) hop / sample_rate, as the offline plan counts them."""
+        return (self.frames_emitted + np.arange(int(f))) * (self._hop / self._sample_rate)
+
+    def reset(self) -> None:
+        """Drop the pending samples; the row count of the next push is free again."""
+        self._check(self._lib.sgx_stream_reset(self._h, None))
+        self._rows, self._squeeze, self._torch = 0, False, None
+
+    def reserve(self, batch: int, max_block: int, host_staging: bool = True) -> None:
+        """Pre-size the stream's buffers so that pushes of up to `max_block` samples on `batch` rows, and the flush, do not allocate.
+        Call it on a stream without pending samples of earlier pushes (after creation, reset or flush)."""
+        self._check(self._lib.sgx_stream_reserve(self._h, int(batch), int(max_block), int(host_staging)))
+
+    # ---- calls ------------------------------------------------------------------------------------------------------------
+    def _cdt(self):
+        return (np.complex64 if self._dt == _ffi.F32 else np.complex128) if self._complex else self._np
+
+    def _tcdt(self):
+        import torch
+        return (torch.complex64 if self._dt == _ffi.F32 else torch.complex128) if self._complex else self._tdt
+
+    def _out_numpy(self, out, shape):
+        if out is None:
+            return np.empty(shape, self._cdt())
+        if tuple(out.shape) != shape:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
+        if out.dtype != self._cdt() or not out.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous with the plan's dtype")
+        return out
+
+    def _out_torch(self, out, shape, device):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=self._tcdt(), device=device)
+        if tuple(out.shape) != shape:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
+        if out.dtype != self._tcdt() or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of the plan's dtype")
+        if not out.is_cuda or out.device.index != self._device:
+            raise ValueError(f"out is on {out.device}, the plan is bound to cuda:{self._device}")
+        return out
+
+    def _elems(self, shape) -> int:
+        return int(np.prod(shape)) * (2 if self._complex else 1)
+
+    def push(self, block, out=None, stream: int = 0):
+        """(C,) or (B, C) new samples -> the frames that became complete, (n_bins, f) or (B, n_bins, f) (complex for a complex plan;
+        f may be 0).  NumPy in -> NumPy out (stream-owned staging, synchronous); a torch tensor on the plan's device -> a tensor
+        there, asynchronous on `stream` / torch's current stream.  `out`, if given, has the shape and dtype of the return value."""
+        if type(block).__module__.startswith("torch"):
+            return self._push_torch(block, out, stream)
+        a = np.ascontiguousarray(block, dtype=self._np)
+        if a.ndim not in (1, 2):
+            raise ValueError("block must be 1-D (n,) or 2-D (batch, n)")
+        xb = a[None] if a.ndim == 1 else a
+        b, c = xb.shape
+        if b == 0:
+            raise ValueError("batch must be > 0")
+        shape = (b, self.n_bins, self.frames(c))
+        res = self._out_numpy(out.reshape(shape) if out is not None and a.ndim == 1 and out.ndim == 2 else out, shape)
+        self._check(self._lib.sgx_stream_push(self._h, xb.ctypes.data, b, c, c, res.ctypes.data if res.size else None,
+                                              self._elems(shape), _ffi.MEM_HOST, None))
+        self._rows, self._squeeze, self._torch = b, a.ndim == 1, None
+        return res[0] if a.ndim == 1 else res
+
+    def _push_torch(self, x, out, stream):
+        import torch
+        if x.dim() not in (1, 2):
+            raise ValueError("block must be 1-D (n,) or 2-D (batch, n)")
+        xb = x[None] if x.dim() == 1 else x
+        if not xb.is_cuda or xb.dtype != self._tdt or xb.stride(1) != 1 and xb.shape[1] > 1:
+            raise ValueError("device path needs a CUDA tensor of the plan's dtype with unit inner stride")
+        if xb.device.index != self._device:
+            raise ValueError(f"block is on {xb.device}, the plan is bound to cuda:{self._device}")
+        b, c = xb.shape
+        if b == 0:
+            raise ValueError("batch must be > 0")
+        shape = (b, self.n_bins, self.frames(c))
+        res = self._out_torch(out.reshape(shape) if out is not None and x.dim() == 1 and out.dim() == 2 else out, shape, xb.device)
+        s = stream or torch.cuda.current_stream(xb.device).cuda_stream
+        stride = xb.stride(0) if b > 1 else max(c, 1)
+        self._check(self._lib.sgx_stream_push(self._h, xb.data_ptr(), b, c, stride, res.data_ptr() if res.numel() else None,
+                                              self._elems(shape), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        self._rows, self._squeeze, self._torch = b, x.dim() == 1, xb.device
+        return res[0] if x.dim() == 1 else res
+
+    def flush(self, out=None, stream: int = 0):
+        """The frames the trailing padding completes, shaped as `push` returns them for the fixed batch (as a tensor on `stream` /
+        the current stream if the last push took one); the stream then starts over with the same row count."""
+        shape = (max(self._rows, 1), self.n_bins, self.flush_frames())
+        sq = self._squeeze or self._rows == 0
+        if self._torch is not None:
+            import torch
+            res = self._out_torch(out.reshape(shape) if out is not None and sq and out.dim() == 2 else out, shape, self._torch)
+            s = stream or torch.cuda.current_stream(self._torch).cuda_stream
+            args = (res.data_ptr() if res.numel() else None, self._elems(shape), _ffi.MEM_DEVICE, C.c_void_p(s))
+        else:
+            res = self._out_numpy(out.reshape(shape) if out is not None and sq and out.ndim == 2 else out, shape)
+            args = (res.ctypes.data if res.size else None, self._elems(shape), _ffi.MEM_HOST, None)
+        self._check(self._lib.sgx_stream_flush(self._h, *args))
+        return res[0] if sq else res
+
+
+__all__ = ["StreamingPlan"]
