@@ -32,7 +32,7 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
@@ -40,10 +40,11 @@
  *    device-pointer call still in flight.  A call does not depend on the calls before it: a larger, smaller, failed, host- or
  *    device-pointer call in between changes neither the bits nor the route of the next one (the DC / Nyquist flag word is
  *    cleared per call; the one exception is the state a streaming plan exists to carry: sgx_fir_process reads and replaces
- *    the plan's history, sgx_stream_push the stream's pending samples, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
+ *    the plan's history, sgx_stream_push the stream's pending samples, sgx_istream_push the stream's overlap tail, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
- *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py).
+ *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py; sgx_istream_push / _flush:
+ *    tests/test_streaming_inverse.py).
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H
@@ -639,6 +640,63 @@ size_t sgx_stream_allocations(const sgx_stream *s);
 const char *sgx_stream_kernel_name(const sgx_stream *s);
 int32_t sgx_stream_device(const sgx_stream *s);
 const char *sgx_stream_last_error(const sgx_stream *s); /* NULL: the text of the last failed create */
+
+/* ---- streaming inverse STFT plans: istft (src/spectrogram.rs:4860-4946) for frames that arrive in runs — the synthesis half of an
+ * analysis -> modify -> synthesis loop on live audio (python/examples/streaming.py).  A stream reads n_fft / hop_size / window /
+ * centre / dtype / device of sgx_params as sgx_istft does (every check of sgx_plan_create applies; SGX_FREQ_CQT is
+ * SGX_INVALID_INPUT) and runs `batch` rows in lock step: every row gets the same number f >= 1 of new frames in a call, and f may
+ * change from call to call.  A call returns the samples that no later frame can change; the unfinished overlap tail stays on the
+ * device.  Let pad = centre ? n_fft / 2 : 0; positions are those of the untrimmed signal; F = the frames taken since creation, reset
+ * or flush; E(F) = (F - 1) hop_size + n_fft.
+ *   hi(F) = max(pad, min(F hop_size, E(F) - pad)),  hi(0) = pad
+ *   sgx_istream_push of f frames   returns positions [hi(F), hi(F + f)) of every row, [batch][m] T; m = 0 is legal: `out` is not
+ *                                  touched (it may be NULL) and out_elems must be 0
+ *   sgx_istream_flush              returns [hi(F), E(F) - pad).  The one exception is the reference's quirk (:4933-4941): centre, even
+ *                                  n_fft and exactly one frame in total give the whole untrimmed frame [0, n_fft).  A stream that has
+ *                                  taken no frame emits nothing.  Then the stream stands as after a reset, except that its row count
+ *                                  stays fixed.
+ * After the flush the samples of all calls, laid end to end, are those of sgx_istft on all frames at once: sgx_istft_length(F)
+ * samples, the same order, equal to rounding.  Bit equality with sgx_istft, or across different cuts, is NOT promised (the rows'
+ * launcher may choose by row count, the paired routes pair the frames of a call, sgx_istft may take a fused kernel).  The arithmetic
+ * per sample is that of sgx_istft's unfused route: the windowed row values of the covering frames added in ascending frame order,
+ * divided by the sum of the rounded w w over all covering frames where that exceeds 1e-10; the carry holds raw partial sums only.
+ * The imaginary parts of the DC bin, and of the Nyquist bin at even n_fft, are ignored on both memory kinds and not reported.
+ * `spec` is [batch][n_bins][bin_stride] complex T (interleaved pairs), frame j of bin k of row b at b n_bins bin_stride + k bin_stride
+ * + j: bin_stride = n_frames is a dense matrix, a larger one a run of frames inside a wider resident matrix (SGX_MEM_DEVICE only;
+ * SGX_MEM_HOST needs bin_stride == n_frames).  n_bins != n_fft / 2 + 1 or a wrong out_elems is SGX_DIM_MISMATCH with the two numbers
+ * in sgx_istream_last_error; n_frames = 0 is SGX_INVALID_INPUT.  The first push after creation or reset fixes the row count; a later
+ * push with another batch is SGX_DIM_MISMATCH (text as sgx_stream_push).  A failed call moves no state.
+ * A call is two launches: the rows of sgx_istft's unfused route into a stream-owned frame scratch, and k_istream_ola (carry + new
+ * frames -> `out` and the second of two stream-owned carry buffers of n_fft T per row).  SGX_MEM_HOST uses stream-owned staging and is
+ * synchronous, SGX_MEM_DEVICE is asynchronous on `stream` (a hipStream_t) and is one operation of that stream; calls that go to
+ * different hipStreams must be ordered by the caller.  sgx_istream_reserve sizes the carry buffers, the frame scratch and
+ * (host_staging) the staging for pushes of up to max_frames frames on `batch` rows and the flush behind them: such calls allocate
+ * nothing and do not synchronise; a larger one replaces a buffer once (it waits for `stream` and the device).  It needs a stream
+ * that carries nothing (after creation, reset or flush).  device -1: the current device, -2: a host-only stream (validation and the
+ * bookkeeping below; push, a flush with frames taken, and reserve return SGX_BACKEND). */
+typedef struct sgx_istream sgx_istream; /* opaque; same single-caller rule as sgx_fir */
+sgx_status sgx_istream_create(const sgx_params *params, sgx_istream **out);
+void sgx_istream_destroy(sgx_istream *s);
+/* Pure bookkeeping (host-only streams too): the samples per row a push of n_frames frames returns on a stream that has taken
+ * frames_taken; n_frames = 0 asks for the flush after frames_taken frames instead. */
+sgx_status sgx_istream_step(const sgx_istream *s, size_t frames_taken, size_t n_frames, size_t *n_samples);
+size_t sgx_istream_frames_taken(const sgx_istream *s);    /* F */
+size_t sgx_istream_samples_emitted(const sgx_istream *s); /* per row, since creation / reset / flush */
+size_t sgx_istream_pending(const sgx_istream *s);         /* samples carried per row, <= n_fft */
+sgx_status sgx_istream_flush_samples(const sgx_istream *s, size_t *n_samples); /* what sgx_istream_flush would return now, per row */
+/* out_elems = batch * m */
+sgx_status sgx_istream_push(sgx_istream *s, const void *spec, size_t batch, size_t n_bins, size_t n_frames, size_t bin_stride, void *out,
+                            size_t out_elems, int32_t mem_kind, void *stream);
+sgx_status sgx_istream_flush(sgx_istream *s, void *out, size_t out_elems, int32_t mem_kind, void *stream);
+/* A dropped carry is never read again, so nothing is enqueued on `stream`. */
+sgx_status sgx_istream_reset(sgx_istream *s, void *stream);
+sgx_status sgx_istream_reserve(sgx_istream *s, size_t batch, size_t max_frames, int32_t host_staging);
+/* A diagnostic: how many times the stream has allocated or replaced one of its own buffers (carry, frame scratch, host staging). */
+size_t sgx_istream_allocations(const sgx_istream *s);
+/* the rows' route of the last call + "+stream_ola", e.g. "c2r_reg+stream_ola"; "" before any call */
+const char *sgx_istream_kernel_name(const sgx_istream *s);
+int32_t sgx_istream_device(const sgx_istream *s);
+const char *sgx_istream_last_error(const sgx_istream *s); /* NULL: the text of the last failed create */
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,7 @@ from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatonePa
                      MfccParams, SpectrogramParams, StftParams, WindowType)
 from .source import ChromaSource, CqtSource, GammatoneSource, MfccSource
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
-from .streaming import StreamingPlan
+from .streaming import StreamingInversePlan, StreamingPlan
 
 # The reference exposes one plan class per (frequency scale, amplitude scale) (python/spectrograms/__init__.pyi:1087-1245);
 # here they are one class parameterised at construction, exported under the same names.
@@ -65,5 +65,5 @@ __all__ = [
     "FirPlan", "OverlapSaveConvolver", "DeconvPlan", "fft_convolve", "fft_deconvolve",
     "MinPhasePlan", "minimum_phase", "minimum_phase_with",
     "cqt", "CqtResult", "CqtTransformPlan", "GammatoneSource", "CqtSource", "ChromaSource", "MfccSource",
-    "StreamingPlan",
+    "StreamingPlan", "StreamingInversePlan",
 ]

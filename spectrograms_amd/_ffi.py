@@ -51,6 +51,9 @@ SYMBOLS = [
     "sgx_stream_create", "sgx_stream_destroy", "sgx_stream_step", "sgx_stream_pending", "sgx_stream_frames_emitted", "sgx_stream_flush_frames",
     "sgx_stream_n_bins", "sgx_stream_push", "sgx_stream_flush", "sgx_stream_reset", "sgx_stream_reserve", "sgx_stream_allocations",
     "sgx_stream_kernel_name", "sgx_stream_device", "sgx_stream_last_error",
+    "sgx_istream_create", "sgx_istream_destroy", "sgx_istream_step", "sgx_istream_frames_taken", "sgx_istream_samples_emitted",
+    "sgx_istream_pending", "sgx_istream_flush_samples", "sgx_istream_push", "sgx_istream_flush", "sgx_istream_reset",
+    "sgx_istream_reserve", "sgx_istream_allocations", "sgx_istream_kernel_name", "sgx_istream_device", "sgx_istream_last_error",
 ]
 
 
@@ -295,6 +298,24 @@ def lib() -> C.CDLL:
     L.sgx_stream_device.restype = C.c_int32
     L.sgx_stream_last_error.argtypes = [vp]
     L.sgx_stream_last_error.restype = C.c_char_p
+    L.sgx_istream_create.argtypes = [C.POINTER(SgxParams), C.POINTER(vp)]
+    L.sgx_istream_destroy.argtypes = [vp]
+    L.sgx_istream_destroy.restype = None
+    L.sgx_istream_step.argtypes = [vp, sz, sz, C.POINTER(sz)]
+    L.sgx_istream_flush_samples.argtypes = [vp, C.POINTER(sz)]
+    for f in (L.sgx_istream_frames_taken, L.sgx_istream_samples_emitted, L.sgx_istream_pending, L.sgx_istream_allocations):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_istream_push.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_istream_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
+    L.sgx_istream_reset.argtypes = [vp, vp]
+    L.sgx_istream_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_istream_kernel_name.argtypes = [vp]
+    L.sgx_istream_kernel_name.restype = C.c_char_p
+    L.sgx_istream_device.argtypes = [vp]
+    L.sgx_istream_device.restype = C.c_int32
+    L.sgx_istream_last_error.argtypes = [vp]
+    L.sgx_istream_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -1299,18 +1299,20 @@ sgx_status inverse_tables(sgx_plan *pl) {
 
 // frames (rows) of `spec` -> real rows of n_fft samples: inverse real FFT, * 1/n in T (fft_backend.rs:559-563), optional window.
 // `*route` is set to the rows' launcher that ran: "c2r_reg", "c2r_chirpz" (two rows per complex sequence), "c2r_chirpz_half",
-// "c2r_rows" (radix-2 / two-factor / direct sum), "big" (two rows per sequence)
-sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_t batch, size_t n_frames, bool frame_fast,
-                             const void *win, hipStream_t s, const char **route) {
+// "c2r_rows" (radix-2 / two-factor / direct sum), "big" (two rows per sequence).  frame_fast: bin k of the frames sits at
+// spec[b nb_fft bin_stride + k bin_stride + frame], bin_stride >= n_frames (n_frames: a dense matrix; more: a run of frames inside a
+// wider resident one, istream.hip).  Declared in sgx_internal.h for istream.hip; the helpers it reads stay in this file.
+}  // namespace
+sgx_status sgx::launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_t batch, size_t n_frames, size_t bin_stride,
+                                  bool frame_fast, const void *win, hipStream_t s, const char **route) {
     const unsigned n = pl->p.n_fft;
     C2rArgs c{};
     c.in = spec; c.out = frames;
     c.nrows = unsigned(n_frames); c.ncols = n; c.batch = unsigned(batch);
     c.log2c = 0;
     if (n >= 2 && !(n & (n - 1))) while ((1u << c.log2c) < n) ++c.log2c;
-    c.in_img = (unsigned long long)pl->nb_fft * n_frames;
-    if (frame_fast) { c.in_ks = n_frames; c.in_rs = 1; c.k_fast = 0; }  // [bin][frame] (StftResult layout, S9)
-    else { c.in_ks = 1; c.in_rs = pl->nb_fft; c.k_fast = 1; }
+    if (frame_fast) { c.in_img = (unsigned long long)pl->nb_fft * bin_stride; c.in_ks = bin_stride; c.in_rs = 1; c.k_fast = 0; }  // [bin][frame] (StftResult layout, S9)
+    else { c.in_img = (unsigned long long)pl->nb_fft * n_frames; c.in_ks = 1; c.in_rs = pl->nb_fft; c.k_fast = 1; }
     if (pl->kind == K_BIGFFT || pl->big.M) {  // rows through global memory (two frames per complex sequence, the forward engine behind conj)
         c.scale = inverse_scale(pl);
         c.win = win;
@@ -1352,6 +1354,7 @@ sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_
     *route = r;
     return SGX_OK;
 }
+namespace {
 
 // `*route` is set to the route that ran (sgx_istft_kernel_name).  Every name it can take — keep tests/test_istft_precision.py's
 // list in step: "istft1024c", "istft2048", "istft_d512", "istft_d1024", "istft_reg", and launch_c2r_frames' rows + k_istft_ola:
@@ -1381,7 +1384,7 @@ sgx_status run_istft(sgx_plan *pl, const void *spec, size_t batch, size_t n_fram
     }
     if ((st = grow(pl, pl->d_frames, batch * n_frames * n * pl->elem)) != SGX_OK) return st;
     const char *rows = "";
-    if ((st = launch_c2r_frames(pl, spec, pl->d_frames, batch, n_frames, true, pl->d_window, s, &rows)) != SGX_OK) return st;
+    if ((st = launch_c2r_frames(pl, spec, pl->d_frames, batch, n_frames, n_frames, true, pl->d_window, s, &rows)) != SGX_OK) return st;
     SGX_TRY_HIP(pl, launch_istft_ola(pl->d_frames, pl->d_window, out, unsigned(n), pl->p.hop_size, unsigned(n_frames), start, out_len,
                                  unsigned(batch), pl->dtype, s));
     static const char *const with_ola[][2] = {{"c2r_reg", "c2r_reg+ola"}, {"c2r_chirpz", "c2r_chirpz+ola"},
@@ -1891,7 +1894,7 @@ sgx_status sgx_c2r(sgx_plan *plan, const void *in, size_t in_len, void *out, siz
     SGX_TRY_HIP(plan, hipMemcpy(plan->d_in, in, 2 * nb * plan->elem, hipMemcpyHostToDevice));
     SGX_TRY_HIP(plan, hipMemsetAsync(plan->d_flag, 0, sizeof(unsigned), nullptr));
     const char *route = "";
-    if ((st = launch_c2r_frames(plan, plan->d_in, plan->d_out, 1, 1, false, nullptr, nullptr, &route)) != SGX_OK) return st;
+    if ((st = launch_c2r_frames(plan, plan->d_in, plan->d_out, 1, 1, 1, false, nullptr, nullptr, &route)) != SGX_OK) return st;
     SGX_TRY_HIP(plan, hipMemcpy(out, plan->d_out, n * plan->elem, hipMemcpyDeviceToHost));
     if ((st = check_flag(plan, nullptr)) == SGX_OK) plan->istft_route = route;
     return st;

@@ -209,6 +209,11 @@ unsigned c2r_tile_for(unsigned n, int dtype, size_t lds_budget);
 // overlap-add + normalisation of windowed frames [batch][n_frames][n] into out[batch][out_len] (istft, spectrogram.rs:4911-4930)
 hipError_t launch_istft_ola(const void *frames, const void *win, void *out, unsigned n, unsigned hop, unsigned n_frames,
                             unsigned long long start, unsigned long long out_len, unsigned batch, int dtype, hipStream_t s);
+// the inverse rows of a plan (plan.hip): `n_frames` spectra per image -> real rows [batch][n_frames][n_fft], * 1/n_fft, * win (null:
+// none), through the launcher the plan's length has ("c2r_reg", "c2r_chirpz", "c2r_chirpz_half", "c2r_rows", "big": *route).
+// frame_fast: [bin][frame] spectra with `bin_stride` elements between bins (sgx_istft: n_frames; istream.hip: the caller's)
+sgx_status launch_c2r_frames(sgx_plan *pl, const void *spec, void *frames, size_t batch, size_t n_frames, size_t bin_stride, bool frame_fast,
+                             const void *win, hipStream_t s, const char **route);
 hipError_t launch_c2c_tile(const C2cArgs &a, int dtype, hipStream_t s);
 hipError_t launch_c2r_rows(const C2rArgs &a, int dtype, hipStream_t s);
 // register-tiled versions (kernels_reg2d.hip); they pick their own tile.  hipErrorNotSupported: no pass split for this length

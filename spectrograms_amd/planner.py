@@ -480,6 +480,14 @@ class Plan:
         from .streaming import StreamingPlan
         return StreamingPlan(self._params, self._amp, self._mel, self._db, self.dtype, self._device, self._mfcc)
 
+    def istream(self):
+        """A `StreamingInversePlan` with this plan's STFT parameters, dtype and device: `istft_batch` for frames that arrive in runs.
+        Complex plans only."""
+        if not self.is_complex:
+            raise ValueError("istream() needs a complex STFT plan")
+        from .streaming import StreamingInversePlan
+        return StreamingInversePlan(self._params, self.dtype, self._device)
+
     def r2c(self, frame) -> np.ndarray:
         """Conforming R2cPlan::process (src/fft_backend.rs:423-431) on one frame of n_fft reals."""
         x = np.ascontiguousarray(frame, dtype=self._np)

@@ -5,6 +5,9 @@ in lock step (any `C` per call) and returns the frames that became complete, `fl
 After the flush the frames of all calls, laid end to end, are those of `Plan.compute_batch` on the whole signals: the same count in
 the same order, equal to rounding (not bit for bit across different cuts: the frame count of a call decides the launch shape).  The
 rows' pending samples stay on the device between calls; the first push after creation or `reset()` fixes `B`.
+
+`StreamingInversePlan` (sgx_istream_*) is the synthesis half: frames in, the samples that no later frame can change out, the overlap
+tail on the device.
 """
 from __future__ import annotations
 
@@ -164,4 +167,148 @@ class StreamingPlan(_ffi.NativeHandle):
         return res[0] if sq else res
 
 
-__all__ = ["StreamingPlan"]
+class StreamingInversePlan(_ffi.NativeHandle):
+    """One sgx_istream: the inverse STFT of `params` (n_fft / hop / window / centre) for frames that arrive in runs.  `push(frames)`
+    hands `(B, n_bins, f)` new frames to `B` rows that run in lock step (any `f >= 1` per call) and returns the samples no later frame
+    can change, `flush()` the rest.  After the flush the samples of all calls, laid end to end, are those of `Plan.istft_batch` on all
+    frames at once: `istft_length(F)` samples in the same order, equal to rounding (not bit for bit).  The unfinished overlap tail stays
+    on the device between calls; the first push after creation or `reset()` fixes `B`.  Not thread-safe, like `Plan`."""
+
+    _prefix = "sgx_istream"
+
+    def __init__(self, params: SpectrogramParams, dtype: Optional[str] = None, device: int = _ffi.DEVICE_CURRENT):
+        self._lib = _ffi.lib()
+        self._dt = parse_dtype(dtype)
+        self._n_bins = params.stft.n_fft // 2 + 1
+        p, cw, _ = flatten_params(params, _ffi.AMP_COMPLEX, None, None, None)  # (cw: the custom window stays alive across the create call)
+        p.dtype, p.device = self._dt, int(device)
+        ptr = C.c_void_p()
+        self._create(self._lib.sgx_istream_create(C.byref(p), C.byref(ptr)), ptr)
+        self._device = int(self._lib.sgx_istream_device(ptr))
+        self._rows = 0          # fixed by the first push; reset() frees it
+        self._squeeze = False   # the pushes are 2-D: the samples come back without the batch axis
+        self._torch = None      # the device of the last pushed tensor (None: NumPy pushes)
+
+    frames_taken = property(lambda self: int(self._lib.sgx_istream_frames_taken(self._h)), doc="frames since creation / reset / flush")
+    samples_emitted = property(lambda self: int(self._lib.sgx_istream_samples_emitted(self._h)), doc="samples returned per row since creation / reset / flush")
+    pending = property(lambda self: int(self._lib.sgx_istream_pending(self._h)), doc="samples carried per row (at most n_fft)")
+    n_bins = property(lambda self: self._n_bins)
+    kernel_name = property(lambda self: self._lib.sgx_istream_kernel_name(self._h).decode(),
+                           doc='the rows\' route of the last call + "+stream_ola"; "" before any call')
+    allocations = property(lambda self: int(self._lib.sgx_istream_allocations(self._h)),
+                           doc="how often the stream has allocated or replaced one of its own buffers (it stands still within what reserve() sized)")
+    device = property(lambda self: self._device)
+    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
+
+    def samples(self, f: int) -> int:
+        """Samples per row a push of `f >= 1` frames would return now."""
+        if int(f) < 1:
+            raise ValueError("f must be >= 1")
+        m = C.c_size_t()
+        self._check(self._lib.sgx_istream_step(self._h, self.frames_taken, int(f), C.byref(m)))
+        return m.value
+
+    def flush_samples(self) -> int:
+        """Samples per row `flush()` would return now."""
+        m = C.c_size_t()
+        self._check(self._lib.sgx_istream_flush_samples(self._h, C.byref(m)))
+        return m.value
+
+    def reset(self) -> None:
+        """Drop the carried tail; the row count of the next push is free again."""
+        self._check(self._lib.sgx_istream_reset(self._h, None))
+        self._rows, self._squeeze, self._torch = 0, False, None
+
+    def reserve(self, batch: int, max_frames: int, host_staging: bool = True) -> None:
+        """Pre-size the stream's buffers so that pushes of up to `max_frames` frames on `batch` rows, and the flush, do not allocate.
+        Call it on a stream that carries nothing (after creation, reset or flush)."""
+        self._check(self._lib.sgx_istream_reserve(self._h, int(batch), int(max_frames), int(host_staging)))
+
+    # ---- calls ------------------------------------------------------------------------------------------------------------
+    def _cdt(self):
+        return np.complex64 if self._dt == _ffi.F32 else np.complex128
+
+    def _out_numpy(self, out, shape):
+        if out is None:
+            return np.empty(shape, self._np)
+        if tuple(out.shape) != shape:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
+        if out.dtype != self._np or not out.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous with the plan's dtype")
+        return out
+
+    def _out_torch(self, out, shape, device):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=self._tdt, device=device)
+        if tuple(out.shape) != shape:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
+        if out.dtype != self._tdt or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of the plan's dtype")
+        if not out.is_cuda or out.device.index != self._device:
+            raise ValueError(f"out is on {out.device}, the plan is bound to cuda:{self._device}")
+        return out
+
+    def push(self, frames, out=None, stream: int = 0):
+        """(n_bins, f) or (B, n_bins, f) new complex frames -> the samples that became final, (m,) or (B, m) (m may be 0).  NumPy in ->
+        NumPy out (stream-owned staging, synchronous); a torch tensor on the plan's device -> a tensor there, asynchronous on `stream`
+        / torch's current stream; it may be a slice `S[:, :, a:b]` of a resident spectrogram (unit inner stride, the bin stride is
+        taken from the tensor).  `out`, if given, has the shape and dtype of the return value."""
+        if type(frames).__module__.startswith("torch"):
+            return self._push_torch(frames, out, stream)
+        a = np.ascontiguousarray(frames, dtype=self._cdt())
+        if a.ndim not in (2, 3):
+            raise ValueError("frames must be 2-D (n_bins, f) or 3-D (batch, n_bins, f)")
+        xb = a[None] if a.ndim == 2 else a
+        b, nb, f = xb.shape
+        if b == 0:
+            raise ValueError("batch must be > 0")
+        shape = (b, self.samples(f) if f and nb == self._n_bins else 0)
+        res = self._out_numpy(out.reshape(shape) if out is not None and a.ndim == 2 and out.ndim == 1 else out, shape)
+        self._check(self._lib.sgx_istream_push(self._h, xb.ctypes.data, b, nb, f, f, res.ctypes.data if res.size else None, res.size,
+                                               _ffi.MEM_HOST, None))
+        self._rows, self._squeeze, self._torch = b, a.ndim == 2, None
+        return res[0] if a.ndim == 2 else res
+
+    def _push_torch(self, x, out, stream):
+        import torch
+        if x.dim() not in (2, 3):
+            raise ValueError("frames must be 2-D (n_bins, f) or 3-D (batch, n_bins, f)")
+        xb = x[None] if x.dim() == 2 else x
+        want = torch.complex64 if self._dt == _ffi.F32 else torch.complex128
+        b, nb, f = xb.shape
+        if not xb.is_cuda or xb.dtype != want or xb.stride(2) != 1 and f > 1:
+            raise ValueError("device path needs a CUDA tensor of the plan's complex dtype with unit inner stride")
+        if xb.device.index != self._device:
+            raise ValueError(f"frames are on {xb.device}, the plan is bound to cuda:{self._device}")
+        if b == 0:
+            raise ValueError("batch must be > 0")
+        bin_stride = xb.stride(1) if nb > 1 else max(f, 1)
+        if bin_stride < f or b > 1 and xb.stride(0) != nb * bin_stride:
+            raise ValueError("device path needs rows of (n_bins, bin_stride) with nothing between them (a slice along the frame axis)")
+        shape = (b, self.samples(f) if f and nb == self._n_bins else 0)
+        res = self._out_torch(out.reshape(shape) if out is not None and x.dim() == 2 and out.dim() == 1 else out, shape, xb.device)
+        s = stream or torch.cuda.current_stream(xb.device).cuda_stream
+        self._check(self._lib.sgx_istream_push(self._h, xb.data_ptr(), b, nb, f, bin_stride, res.data_ptr() if res.numel() else None,
+                                               res.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        self._rows, self._squeeze, self._torch = b, x.dim() == 2, xb.device
+        return res[0] if x.dim() == 2 else res
+
+    def flush(self, out=None, stream: int = 0):
+        """The samples that were waiting for later frames, shaped as `push` returns them for the fixed batch (as a tensor on `stream` /
+        the current stream if the last push took one); the stream then starts over with the same row count."""
+        shape = (max(self._rows, 1), self.flush_samples())
+        sq = self._squeeze or self._rows == 0
+        if self._torch is not None:
+            import torch
+            res = self._out_torch(out.reshape(shape) if out is not None and sq and out.dim() == 1 else out, shape, self._torch)
+            s = stream or torch.cuda.current_stream(self._torch).cuda_stream
+            args = (res.data_ptr() if res.numel() else None, res.numel(), _ffi.MEM_DEVICE, C.c_void_p(s))
+        else:
+            res = self._out_numpy(out.reshape(shape) if out is not None and sq and out.ndim == 1 else out, shape)
+            args = (res.ctypes.data if res.size else None, res.size, _ffi.MEM_HOST, None)
+        self._check(self._lib.sgx_istream_flush(self._h, *args))
+        return res[0] if sq else res
+
+
+__all__ = ["StreamingPlan", "StreamingInversePlan"]
