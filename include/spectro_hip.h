@@ -32,7 +32,7 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush, sgx_resample_resample / _process / _flush / _reset): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
@@ -40,11 +40,11 @@
  *    device-pointer call still in flight.  A call does not depend on the calls before it: a larger, smaller, failed, host- or
  *    device-pointer call in between changes neither the bits nor the route of the next one (the DC / Nyquist flag word is
  *    cleared per call; the one exception is the state a streaming plan exists to carry: sgx_fir_process reads and replaces
- *    the plan's history, sgx_stream_push the stream's pending samples, sgx_istream_push the stream's overlap tail, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
+ *    the plan's history, sgx_stream_push the stream's pending samples, sgx_istream_push the stream's overlap tail, sgx_resample_process the rows' last K - 1 samples, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
  *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py; sgx_istream_push / _flush:
- *    tests/test_streaming_inverse.py).
+ *    tests/test_streaming_inverse.py; the sgx_resample calls: tests/test_resample.py).
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H
@@ -697,6 +697,75 @@ size_t sgx_istream_allocations(const sgx_istream *s);
 const char *sgx_istream_kernel_name(const sgx_istream *s);
 int32_t sgx_istream_device(const sgx_istream *s);
 const char *sgx_istream_last_error(const sgx_istream *s); /* NULL: the text of the last failed create */
+
+/* ---- sample-rate conversion plans: batched band-limited resampling with torchaudio.functional.resample's semantics (the reference
+ * has no resampler; this is the step in front of every plan above when the audio is not at the plan's rate).  Rates are positive
+ * integers; g = gcd(orig_freq, new_freq), M = orig_freq / g (sgx_resample_down), L = new_freq / g (sgx_resample_up), base = min(L, M) rolloff.
+ *   phi(t) = sinc(t) w(t / lpw) for |t| < lpw, 0 otherwise; sinc(t) = sin(pi t) / (pi t), sinc(0) = 1; lpw = lowpass_filter_width
+ *   w(u)   = cos^2(pi u / 2) (SGX_RESAMPLE_SINC_HANN) or I0(beta sqrt(1 - u^2)) / I0(beta) (SGX_RESAMPLE_SINC_KAISER)
+ *   y[m]   = (base / M) sum_n x[n] phi(base (n / M - m / L)),  0 <= m < ceil(n_samples L / M),  x = 0 outside [0, n_samples)
+ * Polyphase form, m = q L + p with 0 <= p < L:  y[q L + p] = sum_{k < K} c[p][k] x[q M + j0(p) + k], where j0(p) is the smallest j with
+ * |base (j / M - p / L)| < lpw (sgx_resample_phase_offsets), K the largest number of such j over p (sgx_resample_taps_per_phase) and
+ * c[p][k] = (base / M) phi(base ((j0(p) + k) / M - p / L)), exactly 0 beyond the support (sgx_resample_taps).  The table is built in f64,
+ * rounded once to T and uploaded.  Equal rates (M = L = 1) are the identity: K = 1, c = [[1]], j0 = [0].
+ * Arithmetic: every output is one chain in T, acc = 0, then acc = fma(c[p][k], x[..], acc) for k = 0 .. K - 1 ascending, on both routes.
+ * The bits of an output therefore depend neither on the route nor on the tiling nor on how a stream is cut into calls, and an output
+ * whose K samples are all zero is exactly zero.
+ *   sgx_resample_resample   stateless, whole rows: out [batch][sgx_resample_out_len(n_samples)].
+ *   sgx_resample_process    streaming: `batch` rows in lock step, n_samples >= 1 new samples per row; returns every output whose whole
+ *                           window is known and that no earlier call returned.  With N = the samples consumed so far (sgx_resample_consumed)
+ *                           and E = the outputs emitted (sgx_resample_emitted), after the call E = #{ m : floor(m / L) M + j0(m mod L)
+ *                           + K - 1 <= N - 1 }; the count is what sgx_resample_step says, it may be 0 (`out` may then be NULL, out_elems 0).
+ *                           The first call after creation, reset or flush fixes the row count; another batch is SGX_DIM_MISMATCH
+ *                           (expected / got in the text) and moves no state.
+ *   sgx_resample_flush      takes the future as zeros and returns the outputs E .. ceil(N L / M) - 1 of every row; then the plan
+ *                           stands as after sgx_resample_reset.  Without a call to sgx_resample_process before it, it returns nothing.
+ * After the flush the outputs of all calls, laid end to end, are bit for bit those of sgx_resample_resample on the whole rows.
+ *   route SGX_RESAMPLE_ROUTE_AUTO, K <= 64, L <= 512 and a tile within 64 KiB of LDS   "k_resample_pp": one fused launch, samples in
+ *                           LDS, a work item's coefficients in registers; sgx_resample_tile outputs per workgroup tile
+ *   otherwise               "resample_generic": table and samples from global memory; L K above 2^22 coefficients is
+ *                           SGX_INVALID_INPUT, the text names the reduced ratio M : L
+ * The device holds each row's last K - 1 samples in one of two plan-owned buffers; the next history is written into the other one and
+ * copied back on `stream`, so no launch reads what it writes.  Rows: row r at x + r * sample_stride (elements of T, sample_stride >=
+ * n_samples); `out` must not overlap `x`; out_elems must be batch * n_out (else SGX_DIM_MISMATCH); mem_kind as sgx_execute, `stream`
+ * a hipStream_t as its hip_stream (the streams paragraph at the top: a device-pointer call is one operation of `stream`, allocates
+ * nothing within what sgx_resample_reserve sized — the device path of sgx_resample_resample never allocates — and can be captured).
+ * Errors (SGX_INVALID_INPUT): rates <= 0, lowpass_filter_width < 1, rolloff outside (0, 1], an unknown method or route, beta not
+ * finite or < 0 (Kaiser).  device -1: the current device, -2: a host-only plan (the table and every accessor below; the compute calls
+ * and reserve return SGX_BACKEND). */
+typedef struct sgx_resample sgx_resample; /* opaque; same single-caller rule as sgx_fir */
+enum { SGX_RESAMPLE_SINC_HANN = 0, SGX_RESAMPLE_SINC_KAISER = 1 };
+enum { SGX_RESAMPLE_ROUTE_AUTO = 0, SGX_RESAMPLE_ROUTE_GENERIC = 1 };
+sgx_status sgx_resample_create(int64_t orig_freq, int64_t new_freq, int32_t lowpass_filter_width, double rolloff, int32_t method, double beta,
+                               int32_t route, int32_t dtype, int32_t device, sgx_resample **out);
+void sgx_resample_destroy(sgx_resample *plan);
+sgx_status sgx_resample_resample(sgx_resample *plan, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out,
+                                 size_t out_elems, int32_t mem_kind, void *stream);
+sgx_status sgx_resample_process(sgx_resample *plan, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out,
+                                size_t out_elems, int32_t mem_kind, void *stream);
+sgx_status sgx_resample_flush(sgx_resample *plan, void *out, size_t out_elems, int32_t mem_kind, void *stream);
+/* Zero history, nothing consumed and no fixed row count again; the zeroing is enqueued on `stream`. */
+sgx_status sgx_resample_reset(sgx_resample *plan, void *stream);
+/* Pre-sizes the history for `batch` rows and, with host_staging, the SGX_MEM_HOST staging for calls of up to max_block samples per row,
+ * so that those calls and the flush behind them do not allocate. */
+sgx_status sgx_resample_reserve(sgx_resample *plan, size_t batch, size_t max_block, int32_t host_staging);
+/* Pure arithmetic (host-only plans too): the outputs per row a call of n_samples samples returns on a stream that has consumed
+ * `consumed`, and what it has consumed afterwards (may be NULL); n_samples = 0 asks for the flush after `consumed` samples instead. */
+sgx_status sgx_resample_step(const sgx_resample *plan, size_t consumed, size_t n_samples, size_t *n_out, size_t *consumed_after);
+size_t sgx_resample_out_len(const sgx_resample *plan, size_t n_samples); /* ceil(n_samples L / M) */
+size_t sgx_resample_up(const sgx_resample *plan);                        /* L */
+size_t sgx_resample_down(const sgx_resample *plan);                      /* M */
+size_t sgx_resample_taps_per_phase(const sgx_resample *plan);            /* K */
+sgx_status sgx_resample_taps(const sgx_resample *plan, double *taps /* [L][K]: the T-valued coefficients */);
+sgx_status sgx_resample_phase_offsets(const sgx_resample *plan, int64_t *offsets /* [L]: j0(p) */);
+size_t sgx_resample_tile(const sgx_resample *plan);      /* outputs per workgroup tile of "k_resample_pp"; 0 on the generic route */
+size_t sgx_resample_consumed(const sgx_resample *plan);  /* N, per row, since creation / reset / flush */
+size_t sgx_resample_emitted(const sgx_resample *plan);   /* E */
+/* A diagnostic: how many times the plan has allocated or replaced one of its own buffers (history, host staging). */
+size_t sgx_resample_allocations(const sgx_resample *plan);
+const char *sgx_resample_kernel_name(const sgx_resample *plan); /* "k_resample_pp" or "resample_generic" */
+int32_t sgx_resample_device(const sgx_resample *plan);
+const char *sgx_resample_last_error(const sgx_resample *plan); /* NULL plan: the text of the last failed create */
 
 #ifdef __cplusplus
 }

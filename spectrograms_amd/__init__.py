@@ -28,6 +28,7 @@ from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .minphase import MinPhasePlan, minimum_phase, minimum_phase_with
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
                      MfccParams, SpectrogramParams, StftParams, WindowType)
+from .resample import ResamplePlan, resample
 from .source import ChromaSource, CqtSource, GammatoneSource, MfccSource
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
 from .streaming import StreamingInversePlan, StreamingPlan
@@ -65,5 +66,5 @@ __all__ = [
     "FirPlan", "OverlapSaveConvolver", "DeconvPlan", "fft_convolve", "fft_deconvolve",
     "MinPhasePlan", "minimum_phase", "minimum_phase_with",
     "cqt", "CqtResult", "CqtTransformPlan", "GammatoneSource", "CqtSource", "ChromaSource", "MfccSource",
-    "StreamingPlan", "StreamingInversePlan",
+    "StreamingPlan", "StreamingInversePlan", "ResamplePlan", "resample",
 ]

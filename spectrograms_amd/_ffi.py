@@ -24,6 +24,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 DEVICE_CURRENT, DEVICE_HOST_ONLY = -1, -2
 FIR_ROUTE_AUTO, FIR_ROUTE_GENERIC = 0, 1
 MINPHASE_ROUTE_AUTO, MINPHASE_ROUTE_GENERIC = 0, 1
+RESAMPLE_ROUTE_AUTO, RESAMPLE_ROUTE_GENERIC = 0, 1
+RESAMPLE_SINC_HANN, RESAMPLE_SINC_KAISER = 0, 1
 
 # every symbol include/spectro_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -54,6 +56,10 @@ SYMBOLS = [
     "sgx_istream_create", "sgx_istream_destroy", "sgx_istream_step", "sgx_istream_frames_taken", "sgx_istream_samples_emitted",
     "sgx_istream_pending", "sgx_istream_flush_samples", "sgx_istream_push", "sgx_istream_flush", "sgx_istream_reset",
     "sgx_istream_reserve", "sgx_istream_allocations", "sgx_istream_kernel_name", "sgx_istream_device", "sgx_istream_last_error",
+    "sgx_resample_create", "sgx_resample_destroy", "sgx_resample_resample", "sgx_resample_process", "sgx_resample_flush", "sgx_resample_reset",
+    "sgx_resample_reserve", "sgx_resample_step", "sgx_resample_out_len", "sgx_resample_up", "sgx_resample_down", "sgx_resample_taps_per_phase",
+    "sgx_resample_taps", "sgx_resample_phase_offsets", "sgx_resample_tile", "sgx_resample_consumed", "sgx_resample_emitted",
+    "sgx_resample_allocations", "sgx_resample_kernel_name", "sgx_resample_device", "sgx_resample_last_error",
 ]
 
 
@@ -316,6 +322,30 @@ def lib() -> C.CDLL:
     L.sgx_istream_device.restype = C.c_int32
     L.sgx_istream_last_error.argtypes = [vp]
     L.sgx_istream_last_error.restype = C.c_char_p
+    L.sgx_resample_create.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(vp)]
+    L.sgx_resample_destroy.argtypes = [vp]
+    L.sgx_resample_destroy.restype = None
+    L.sgx_resample_resample.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_resample_process.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_resample_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
+    L.sgx_resample_reset.argtypes = [vp, vp]
+    L.sgx_resample_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_resample_step.argtypes = [vp, sz, sz, C.POINTER(sz), C.POINTER(sz)]
+    L.sgx_resample_out_len.argtypes = [vp, sz]
+    L.sgx_resample_out_len.restype = sz
+    for f in (L.sgx_resample_up, L.sgx_resample_down, L.sgx_resample_taps_per_phase, L.sgx_resample_tile, L.sgx_resample_consumed,
+              L.sgx_resample_emitted, L.sgx_resample_allocations):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_resample_taps.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_resample_phase_offsets.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.sgx_resample_kernel_name.argtypes = [vp]
+    L.sgx_resample_kernel_name.restype = C.c_char_p
+    L.sgx_resample_device.argtypes = [vp]
+    L.sgx_resample_device.restype = C.c_int32
+    L.sgx_resample_last_error.argtypes = [vp]
+    L.sgx_resample_last_error.restype = C.c_char_p
     _lib = L
     return L
 
