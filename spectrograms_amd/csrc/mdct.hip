@@ -647,6 +647,9 @@ sgx_status sgx_mdct_create(size_t window_size, size_t hop_size, int32_t window_k
     p->fused_fwd = false;
 #else
     p->fused_fwd = N % 2 == 0 && fused_frame_bytes(unsigned(M), dtype, &fa, &fb, &fc) != 0 && fused_ltile(unsigned(M), dtype, 0, false) >= 0;
+    // k_mdct_fwd indexes a tile's samples in 32 bits (so + i, so = s hop, s <= 31, i < 2N): a hop past that takes the generic fold,
+    // whose f hop is 64-bit
+    if (31ull * hop_size + window_size > (1ull << 32)) p->fused_fwd = false;
 #endif
     p->fused_inv = p->fused_fwd && hop_size == N && fused_ltile(unsigned(M), dtype, 0, true) >= 2;
     p->L = unsigned(N % 2 == 0 ? M : N);

@@ -7,6 +7,7 @@ which a CPU test pins against the direct sums.  Deterministic normwise bounds, u
   inverse              max_n |dy[n]|   <= c u_T log2(2N) ceil(2N / hop) max|w| max_f 2 ||C_f||_2 / sqrt(N)
 """
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -26,12 +27,15 @@ WORST = {}
 _PI_LD = np.longdouble("3.14159265358979323846264338327950288")
 
 
+@functools.lru_cache(maxsize=2)  # (the long-double matrix of N = 2048 takes seconds; callers only read it)
 def _cosm(N, dt):
     n = np.arange(2 * N, dtype=np.int64)
     k = np.arange(N, dtype=np.int64)
     r = np.outer(2 * k + 1, 2 * n + 1 + N) % (8 * N)
     pi = _PI_LD if dt is np.longdouble else np.float64(np.pi)
-    return np.cos(r.astype(dt) * pi / dt(4 * N))
+    m = np.cos(r.astype(dt) * pi / dt(4 * N))
+    m.setflags(write=False)
+    return m
 
 
 def frames_of(x, two_n, hop):
@@ -205,18 +209,31 @@ _MIXED = [40, 60, 80, 100, 120, 160, 200, 240, 300, 320, 400, 480, 500, 600, 720
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_kernel_name_selects_fused_route(dtype):
+    from tests import test_mdct_readback as RB  # (imports this module: not at the top)
     fused_m = {1 << p for p in range(4, 13)} | set(_MIXED)
     for ws in list(range(4, 700, 2)) + [960, 1000, 1920, 2048, 2560, 4096, 4094, 5120, 8190, 8192, 16384]:
         M = ws // 4 if ws % 4 == 0 else None
         fused = M in fused_m
         p = sg.MdctPlan(sg.MdctParams(ws, ws // 2, sg.WindowType.hanning), dtype, device=HOST)
         assert p.kernel_name() == ("k_mdct_fwd" if fused else "mdct_generic"), ws
-        assert p.kernel_name(inverse=True).endswith("imdct_ola") == (fused and p.kernel_name(True) == "k_imdct_ola")
+        # hop == N: fused iff at least 4 frames of this split fit in the tile's 72 KiB (the table restated in test_mdct_readback)
+        inst = RB.instance(ws, dtype)
+        assert (inst is not None) == fused, ws
+        assert p.kernel_name(inverse=True) == ("k_imdct_ola" if fused and inst[2] >= 4 else "imdct_generic"), (ws, dtype)
         p2 = sg.MdctPlan(sg.MdctParams(ws, ws // 2 + 1, sg.WindowType.hanning), dtype, device=HOST)
         assert p2.kernel_name(inverse=True) == "imdct_generic"
     for ws in (64, 256, 960, 1920, 2048, 4096):
         p = sg.MdctPlan(sg.MdctParams.sine_window(ws), dtype, device=HOST)
         assert p.kernel_name(True) == "k_imdct_ola", ws
+    # the 4-frame tile is the smallest the fused inverse takes; 2 frames or 1 run the generic route at hop == N
+    generic_at_hop_n = {"float32": {16384}, "float64": {4800, 5120, 8192, 16384}}[dtype]
+    for ws in (4320, 4800, 5120, 8192, 16384):
+        p = sg.MdctPlan(sg.MdctParams.sine_window(ws), dtype, device=HOST)
+        assert p.kernel_name() == "k_mdct_fwd", ws
+        assert p.kernel_name(True) == ("imdct_generic" if ws in generic_at_hop_n else "k_imdct_ola"), (ws, dtype)
+    assert sg.MdctPlan(sg.MdctParams.sine_window(8192), "float32", device=HOST).kernel_name(True) == "k_imdct_ola"
+    for dt, ws in (("float32", 16384), ("float64", 8192), ("float64", 5120), ("float64", 4800)):
+        assert sg.MdctPlan(sg.MdctParams.sine_window(ws), dt, device=HOST).kernel_name(True) == "imdct_generic", (dt, ws)
 
 
 def test_symbols_exported():
