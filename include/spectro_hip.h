@@ -32,7 +32,7 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush, sgx_resample_resample / _process / _flush / _reset): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush, sgx_resample_resample / _process / _flush / _reset, sgx_welch_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
@@ -44,7 +44,7 @@
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
  *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py; sgx_istream_push / _flush:
- *    tests/test_streaming_inverse.py; the sgx_resample calls: tests/test_resample.py).
+ *    tests/test_streaming_inverse.py; the sgx_resample calls: tests/test_resample.py; sgx_welch_execute: tests/test_welch.py).
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H
@@ -766,6 +766,62 @@ size_t sgx_resample_allocations(const sgx_resample *plan);
 const char *sgx_resample_kernel_name(const sgx_resample *plan); /* "k_resample_pp" or "resample_generic" */
 int32_t sgx_resample_device(const sgx_resample *plan);
 const char *sgx_resample_last_error(const sgx_resample *plan); /* NULL plan: the text of the last failed create */
+
+/* ---- Welch plans: batched spectrum estimates of whole signals — the averaged periodogram (PSD), the cross-spectral density of two
+ * signals (CSD) and their magnitude-squared coherence — with the semantics of scipy.signal.welch / csd / coherence for real input
+ * (nfft = nperseg = n_fft, noverlap = n_fft - hop_size, average = "mean", one-sided).  The reference has no such estimate; every
+ * forward plan above ends in a [bins][frames] map.
+ *   segments  s = 0 .. m - 1 hold the samples [s hop, s hop + n_fft), m = 1 + (n_samples - n_fft) / hop (sgx_welch_n_segments): no
+ *             padding (params->centre must be 0), a tail that fills no segment is ignored; n_samples < n_fft is SGX_DIM_MISMATCH
+ *             (scipy shrinks the segment instead)
+ *   X_s       = FFT(w (x_s - trend_s)): the detrend comes first — nothing, the segment's mean, or its least-squares line — then the
+ *             window (any window of sgx_params, custom tables included; SGX_WIN_HANNING is the symmetric Hann, scipy's "hann" string
+ *             the periodic one)
+ *   PSD       Pxx[k] = g_k scale mean_s |X_s[k]|^2                  out [batch][n_bins] T
+ *   CSD       Pxy[k] = g_k scale mean_s conj(X_s[k]) Y_s[k]         out [batch][n_bins] interleaved (re, im) pairs of T
+ *   COHERENCE C[k]   = |Pxy[k]|^2 / (Pxx[k] Pyy[k])                 out [batch][n_bins] T; all three sums come from one pass
+ *   g_k = 2 except g_0 = 1 and, for even n_fft, g_{n_fft/2} = 1; scale = 1 / (sample_rate sum w^2) for SGX_WELCH_DENSITY and
+ *   1 / (sum w)^2 for SGX_WELCH_SPECTRUM, computed in f64 on the host (sgx_welch_scale).
+ * Routes: "k_welch" (SGX_WELCH_ROUTE_AUTO, n_fft a power of two 256 .. 4096): one fused launch that keeps the running sums on chip and
+ * stores no segment's spectrum — a workgroup takes a tile of sgx_welch_tile consecutive segments of one row and leaves one partial in
+ * plan scratch, a second small launch adds a row's partials in tile order; "welch_generic" (every other n_fft an sgx_plan accepts,
+ * and any n_fft with SGX_WELCH_ROUTE_GENERIC): segments gathered to scratch, transformed by an internal plan and added in segment
+ * order, over chunks of at most max_scratch_bytes per buffer (0: 256 MiB).  Neither route uses atomics: a row's result is the same
+ * bits whatever the batch size, the row's place in the batch and the number of calls; on the generic route also whatever the chunk size.
+ * conj(X) X is formed unfused, so the CSD of a signal with itself has a zero imaginary part and the PSD's bits as its real part, and
+ * swapping x and y conjugates the CSD bit for bit.
+ * Rows: row r at x + r * sample_stride (y likewise; elements of T, sample_stride >= n_samples); y must be NULL for a PSD plan and
+ * non-NULL otherwise (SGX_INVALID_INPUT); out_elems must be batch * n_bins (CSD: twice that) else SGX_DIM_MISMATCH; mem_kind as
+ * sgx_execute, `stream` a hipStream_t as its hip_stream.  Not offered: average = "median", zero padding to nfft > nperseg, two-sided
+ * or complex input, sums carried across calls.
+ * Errors (SGX_INVALID_INPUT): centre != 0, an unknown kind, detrend, scaling or route, and every STFT check of sgx_plan_create
+ * (n_fft, hop_size in 1 .. n_fft, the window, the sample rate).  device -1: the current device, -2: a host-only plan (every accessor
+ * below; execute and reserve return SGX_BACKEND behind their shape checks). */
+typedef struct sgx_welch sgx_welch; /* opaque; same single-caller rule as sgx_fir */
+enum { SGX_WELCH_PSD = 0, SGX_WELCH_CSD = 1, SGX_WELCH_COHERENCE = 2 };
+enum { SGX_WELCH_DETREND_NONE = 0, SGX_WELCH_DETREND_CONSTANT = 1, SGX_WELCH_DETREND_LINEAR = 2 };
+enum { SGX_WELCH_DENSITY = 0, SGX_WELCH_SPECTRUM = 1 };
+enum { SGX_WELCH_ROUTE_AUTO = 0, SGX_WELCH_ROUTE_GENERIC = 1 };
+/* Reads n_fft, hop_size, centre, the window fields, sample_rate_hz, dtype and device of `params`. */
+sgx_status sgx_welch_create(const sgx_params *params, int32_t kind, int32_t detrend, int32_t scaling, int32_t route, size_t max_scratch_bytes,
+                            sgx_welch **out);
+void sgx_welch_destroy(sgx_welch *plan);
+size_t sgx_welch_n_bins(const sgx_welch *plan);                        /* n_fft / 2 + 1 */
+size_t sgx_welch_n_segments(const sgx_welch *plan, size_t n_samples);  /* m; 0 when n_samples < n_fft */
+sgx_status sgx_welch_frequencies(const sgx_welch *plan, double *freqs /* [n_bins]: k sample_rate / n_fft */);
+sgx_status sgx_welch_window(const sgx_welch *plan, double *window /* [n_fft]: as built in f64, before the cast to T */);
+double sgx_welch_scale(const sgx_welch *plan);                         /* the f64 factor `scale` above */
+sgx_status sgx_welch_execute(sgx_welch *plan, const void *x, const void *y, size_t batch, size_t n_samples, size_t sample_stride, void *out,
+                             size_t out_elems, int32_t mem_kind, void *stream);
+/* Pre-sizes the partials (generic route: the chunk's scratch and the internal plan's) and, with host_staging, the SGX_MEM_HOST staging
+ * for calls of up to `batch` rows of n_samples samples, so that those calls do not allocate. */
+sgx_status sgx_welch_reserve(sgx_welch *plan, size_t batch, size_t n_samples, int32_t host_staging);
+/* A diagnostic: how many times the plan has allocated or replaced one of its own buffers. */
+size_t sgx_welch_allocations(const sgx_welch *plan);
+size_t sgx_welch_tile(const sgx_welch *plan);             /* segments per workgroup tile of "k_welch"; 0 on the generic route */
+const char *sgx_welch_kernel_name(const sgx_welch *plan); /* "k_welch" or "welch_generic" */
+int32_t sgx_welch_device(const sgx_welch *plan);
+const char *sgx_welch_last_error(const sgx_welch *plan); /* NULL plan: the text of the last failed create */
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ from .resample import ResamplePlan, resample
 from .source import ChromaSource, CqtSource, GammatoneSource, MfccSource
 from .planner import Chromagram, Mfcc, Plan, Spectrogram, SpectrogramBatch, SpectrogramPlanner, StftResult
 from .streaming import StreamingInversePlan, StreamingPlan
+from .welch import WelchParams, WelchPlan, coherence, csd, welch
 
 # The reference exposes one plan class per (frequency scale, amplitude scale) (python/spectrograms/__init__.pyi:1087-1245);
 # here they are one class parameterised at construction, exported under the same names.
@@ -67,4 +68,5 @@ __all__ = [
     "MinPhasePlan", "minimum_phase", "minimum_phase_with",
     "cqt", "CqtResult", "CqtTransformPlan", "GammatoneSource", "CqtSource", "ChromaSource", "MfccSource",
     "StreamingPlan", "StreamingInversePlan", "ResamplePlan", "resample",
+    "WelchParams", "WelchPlan", "welch", "csd", "coherence",
 ]

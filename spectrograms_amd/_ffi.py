@@ -26,6 +26,10 @@ FIR_ROUTE_AUTO, FIR_ROUTE_GENERIC = 0, 1
 MINPHASE_ROUTE_AUTO, MINPHASE_ROUTE_GENERIC = 0, 1
 RESAMPLE_ROUTE_AUTO, RESAMPLE_ROUTE_GENERIC = 0, 1
 RESAMPLE_SINC_HANN, RESAMPLE_SINC_KAISER = 0, 1
+WELCH_PSD, WELCH_CSD, WELCH_COHERENCE = 0, 1, 2
+WELCH_DETREND_NONE, WELCH_DETREND_CONSTANT, WELCH_DETREND_LINEAR = 0, 1, 2
+WELCH_DENSITY, WELCH_SPECTRUM = 0, 1
+WELCH_ROUTE_AUTO, WELCH_ROUTE_GENERIC = 0, 1
 
 # every symbol include/spectro_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -60,6 +64,9 @@ SYMBOLS = [
     "sgx_resample_reserve", "sgx_resample_step", "sgx_resample_out_len", "sgx_resample_up", "sgx_resample_down", "sgx_resample_taps_per_phase",
     "sgx_resample_taps", "sgx_resample_phase_offsets", "sgx_resample_tile", "sgx_resample_consumed", "sgx_resample_emitted",
     "sgx_resample_allocations", "sgx_resample_kernel_name", "sgx_resample_device", "sgx_resample_last_error",
+    "sgx_welch_create", "sgx_welch_destroy", "sgx_welch_n_bins", "sgx_welch_n_segments", "sgx_welch_frequencies", "sgx_welch_window",
+    "sgx_welch_scale", "sgx_welch_execute", "sgx_welch_reserve", "sgx_welch_allocations", "sgx_welch_tile", "sgx_welch_kernel_name",
+    "sgx_welch_device", "sgx_welch_last_error",
 ]
 
 
@@ -346,6 +353,26 @@ def lib() -> C.CDLL:
     L.sgx_resample_device.restype = C.c_int32
     L.sgx_resample_last_error.argtypes = [vp]
     L.sgx_resample_last_error.restype = C.c_char_p
+    L.sgx_welch_create.argtypes = [C.POINTER(SgxParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, sz, C.POINTER(vp)]
+    L.sgx_welch_destroy.argtypes = [vp]
+    L.sgx_welch_destroy.restype = None
+    for f in (L.sgx_welch_n_bins, L.sgx_welch_allocations, L.sgx_welch_tile):
+        f.argtypes = [vp]
+        f.restype = sz
+    L.sgx_welch_n_segments.argtypes = [vp, sz]
+    L.sgx_welch_n_segments.restype = sz
+    L.sgx_welch_frequencies.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_welch_window.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_welch_scale.argtypes = [vp]
+    L.sgx_welch_scale.restype = C.c_double
+    L.sgx_welch_execute.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
+    L.sgx_welch_reserve.argtypes = [vp, sz, sz, C.c_int32]
+    L.sgx_welch_kernel_name.argtypes = [vp]
+    L.sgx_welch_kernel_name.restype = C.c_char_p
+    L.sgx_welch_device.argtypes = [vp]
+    L.sgx_welch_device.restype = C.c_int32
+    L.sgx_welch_last_error.argtypes = [vp]
+    L.sgx_welch_last_error.restype = C.c_char_p
     _lib = L
     return L
 

@@ -58,12 +58,14 @@ def Plan(params, amp, mapping, db, dtype, mfcc=None, inverse=False):
 
 
 def clear_fft_plan_cache() -> None:
-    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct, the binaural, the gammatone and the cqt() plans included."""
+    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct, the binaural, the gammatone, the cqt() and the Welch plans included."""
     from .binaural import clear_binaural_plan_cache
     from .cqt import clear_cqt_plan_cache
     from .gammatone import clear_gammatone_plan_cache
     from .mdct import clear_mdct_plan_cache
+    from .welch import clear_welch_plan_cache
     _PLAN_CACHE.clear()
+    clear_welch_plan_cache()
     clear_mdct_plan_cache()
     clear_binaural_plan_cache()
     clear_gammatone_plan_cache()
