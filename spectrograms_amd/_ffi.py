@@ -31,45 +31,6 @@ WELCH_DETREND_NONE, WELCH_DETREND_CONSTANT, WELCH_DETREND_LINEAR = 0, 1, 2
 WELCH_DENSITY, WELCH_SPECTRUM = 0, 1
 WELCH_ROUTE_AUTO, WELCH_ROUTE_GENERIC = 0, 1
 
-# every symbol include/spectro_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "sgx_plan_create", "sgx_plan_destroy", "sgx_output_shape", "sgx_execute", "sgx_execute_timed", "sgx_axes",
-    "sgx_r2c", "sgx_c2r", "sgx_istft", "sgx_istft_length", "sgx_window", "sgx_mel_weights", "sgx_shard_range", "sgx_last_error", "sgx_last_create_error",
-    "sgx_kernel_name", "sgx_istft_kernel_name", "sgx_bank_stage_name", "sgx_abi_version", "sgx_device_count",
-    "sgx_fft2d_create", "sgx_fft2d_destroy", "sgx_fft2d_forward", "sgx_fft2d_inverse", "sgx_fft2d_convolve",
-    "sgx_fft2d_filter", "sgx_fft2d_last_error", "sgx_fft2d_reserve", "sgx_fft2d_device", "sgx_fft2d_kernel_name",
-    "sgx_reserve", "sgx_plan_device", "sgx_last_dim_mismatch",
-    "sgx_c2c_create", "sgx_c2c_destroy", "sgx_c2c_forward", "sgx_c2c_inverse", "sgx_c2c_last_error",
-    "sgx_comm_unique_id", "sgx_comm_create", "sgx_comm_adopt", "sgx_comm_destroy", "sgx_comm_last_error", "sgx_gather", "sgx_shard_execute", "sgx_shard_execute_chunked",
-    "sgx_membench", "sgx_clock_probe", "sgx_plan_create_cqt", "sgx_cqt_kernels", "sgx_plan_create_cqt_transform", "sgx_cqt_set_route",
-    "sgx_mdct_create", "sgx_mdct_destroy", "sgx_mdct_output_shape", "sgx_mdct_inverse_length", "sgx_mdct_forward", "sgx_mdct_inverse",
-    "sgx_mdct_reserve", "sgx_mdct_window", "sgx_mdct_kernel_name", "sgx_mdct_device", "sgx_mdct_last_error",
-    "sgx_binaural_create", "sgx_binaural_destroy", "sgx_binaural_output_shape", "sgx_binaural_axes", "sgx_binaural_execute",
-    "sgx_binaural_histogram", "sgx_binaural_reserve", "sgx_binaural_kernel_name", "sgx_binaural_device", "sgx_binaural_last_error",
-    "sgx_gammatone_create", "sgx_gammatone_destroy", "sgx_gammatone_output_shape", "sgx_gammatone_execute", "sgx_gammatone_center_frequencies",
-    "sgx_gammatone_coefficients", "sgx_gammatone_reserve", "sgx_gammatone_kernel_name", "sgx_gammatone_device", "sgx_gammatone_last_error",
-    "sgx_fir_create", "sgx_fir_destroy", "sgx_fir_process", "sgx_fir_convolve", "sgx_fir_reset", "sgx_fir_reserve", "sgx_fir_fft_size",
-    "sgx_fir_step", "sgx_fir_taps", "sgx_fir_kernel_name", "sgx_fir_device", "sgx_fir_last_error",
-    "sgx_deconv_create", "sgx_deconv_destroy", "sgx_deconv_output_length", "sgx_deconv_execute", "sgx_deconv_reserve",
-    "sgx_deconv_device", "sgx_deconv_last_error",
-    "sgx_minphase_create", "sgx_minphase_destroy", "sgx_minphase_execute", "sgx_minphase_reserve", "sgx_minphase_fft_size",
-    "sgx_minphase_output_length", "sgx_minphase_taps", "sgx_minphase_kernel_name", "sgx_minphase_device", "sgx_minphase_last_error",
-    "sgx_stream_create", "sgx_stream_destroy", "sgx_stream_step", "sgx_stream_pending", "sgx_stream_frames_emitted", "sgx_stream_flush_frames",
-    "sgx_stream_n_bins", "sgx_stream_push", "sgx_stream_flush", "sgx_stream_reset", "sgx_stream_reserve", "sgx_stream_allocations",
-    "sgx_stream_kernel_name", "sgx_stream_device", "sgx_stream_last_error",
-    "sgx_istream_create", "sgx_istream_destroy", "sgx_istream_step", "sgx_istream_frames_taken", "sgx_istream_samples_emitted",
-    "sgx_istream_pending", "sgx_istream_flush_samples", "sgx_istream_push", "sgx_istream_flush", "sgx_istream_reset",
-    "sgx_istream_reserve", "sgx_istream_allocations", "sgx_istream_kernel_name", "sgx_istream_device", "sgx_istream_last_error",
-    "sgx_resample_create", "sgx_resample_destroy", "sgx_resample_resample", "sgx_resample_process", "sgx_resample_flush", "sgx_resample_reset",
-    "sgx_resample_reserve", "sgx_resample_step", "sgx_resample_out_len", "sgx_resample_up", "sgx_resample_down", "sgx_resample_taps_per_phase",
-    "sgx_resample_taps", "sgx_resample_phase_offsets", "sgx_resample_tile", "sgx_resample_consumed", "sgx_resample_emitted",
-    "sgx_resample_allocations", "sgx_resample_kernel_name", "sgx_resample_device", "sgx_resample_last_error",
-    "sgx_welch_create", "sgx_welch_destroy", "sgx_welch_n_bins", "sgx_welch_n_segments", "sgx_welch_frequencies", "sgx_welch_window",
-    "sgx_welch_scale", "sgx_welch_execute", "sgx_welch_reserve", "sgx_welch_allocations", "sgx_welch_tile", "sgx_welch_kernel_name",
-    "sgx_welch_device", "sgx_welch_last_error",
-]
-
-
 class SgxParams(C.Structure):
     _fields_ = [
         ("n_fft", C.c_uint32), ("hop_size", C.c_uint32), ("centre", C.c_int32), ("window_kind", C.c_int32),
@@ -95,6 +56,162 @@ BINAURAL_ITD, BINAURAL_IPD, BINAURAL_ILD, BINAURAL_ILR = range(4)
 class SgxBinauralParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("start_freq", C.c_double), ("end_freq", C.c_double), ("magphase_power", C.c_uint32),
                 ("wrapped", C.c_int32)]
+
+
+# ---- the C ABI, once: name -> (restype, argtypes), grouped by family as include/spectro_hip.h is.  lib() applies it; tests/test_abi.py
+# checks it against the header's declarations, parameter by parameter.  A new family adds its block here and nowhere else.
+_vp, _sz, _i32, _u32, _i64, _f64, _str = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_int64, C.c_double, C.c_char_p
+_P = C.POINTER
+_ST = C.c_int  # sgx_status
+_EXEC = [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _i32, _vp]  # plan, in, batch, n, stride, out, out_elems, mem_kind, stream
+_FLUSH = [_vp, _vp, _sz, _i32, _vp]                     # plan, out, out_elems, mem_kind, stream
+_RESERVE = [_vp, _sz, _sz, _i32]                        # plan, batch, n, host_staging
+
+
+def _family(prefix, sizes=(), kernel_name=True, device=True):
+    """What every family declares alike: <prefix>_destroy, _last_error, _device, _kernel_name and its size_t getters."""
+    d = {f"{prefix}_destroy": (None, [_vp]), f"{prefix}_last_error": (_str, [_vp])}
+    if device:
+        d[f"{prefix}_device"] = (_i32, [_vp])
+    if kernel_name:
+        d[f"{prefix}_kernel_name"] = (_str, [_vp])
+    d.update({f"{prefix}_{g}": (_sz, [_vp]) for g in sizes})
+    return d
+
+
+SIGNATURES = {
+    # spectrogram plans (sgx_plan)
+    "sgx_plan_create": (_ST, [_P(SgxParams), _P(_vp)]),
+    "sgx_plan_destroy": (None, [_vp]),
+    "sgx_plan_create_cqt": (_ST, [_P(SgxParams), _P(SgxCqtParams), _P(_vp)]),
+    "sgx_plan_create_cqt_transform": (_ST, [_P(SgxParams), _P(SgxCqtParams), _P(_vp)]),
+    "sgx_cqt_set_route": (_ST, [_vp, _i32]),
+    "sgx_cqt_kernels": (_ST, [_vp, _P(_sz), _P(_u32), _P(_f64), _P(_f64)]),
+    "sgx_output_shape": (_ST, [_vp, _sz, _P(_sz), _P(_sz)]),
+    "sgx_execute": (_ST, _EXEC),
+    "sgx_execute_timed": (_ST, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _i32, _P(C.c_float)]),
+    "sgx_axes": (_ST, [_vp, _sz, _P(_f64), _P(_f64)]),
+    "sgx_r2c": (_ST, [_vp, _vp, _sz, _vp, _sz]),
+    "sgx_c2r": (_ST, [_vp, _vp, _sz, _vp, _sz]),
+    "sgx_istft_length": (_ST, [_vp, _sz, _P(_sz)]),
+    "sgx_istft": (_ST, _EXEC),
+    "sgx_window": (_ST, [_vp, _P(_f64)]),
+    "sgx_mel_weights": (_ST, [_vp, _P(_sz), _P(_u32), _P(_u32), _P(_f64)]),
+    "sgx_reserve": (_ST, [_vp, _sz, _sz, _i32, _i32]),
+    "sgx_plan_device": (_i32, [_vp]),
+    "sgx_last_dim_mismatch": (_ST, [_vp, _P(_sz), _P(_sz)]),
+    "sgx_last_error": (_str, [_vp]),
+    "sgx_last_create_error": (_str, []),
+    "sgx_kernel_name": (_str, [_vp]),
+    "sgx_istft_kernel_name": (_str, [_vp]),
+    "sgx_bank_stage_name": (_str, [_vp]),
+    "sgx_abi_version": (_i32, []),
+    "sgx_device_count": (_i32, []),
+    "sgx_membench": (_ST, [_i32, _sz, _i32, _i32, _P(_f64)]),
+    "sgx_clock_probe": (_ST, [_i32, _vp, _P(_f64)]),
+    # sharding (sgx_comm)
+    "sgx_shard_range": (_ST, [_sz, _i32, _i32, _P(_sz), _P(_sz)]),
+    "sgx_comm_unique_id": (_ST, [_vp]),
+    "sgx_comm_create": (_ST, [_vp, _i32, _i32, _i32, _P(_vp)]),
+    "sgx_comm_adopt": (_ST, [_vp, _i32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_comm", kernel_name=False, device=False),
+    "sgx_gather": (_ST, [_vp, _vp, _vp, _sz, _sz, _i32, _vp]),
+    "sgx_shard_execute": (_ST, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
+    "sgx_shard_execute_chunked": (_ST, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _i32, _vp]),
+    # 2-D FFT (sgx_fft2d) and 1-D complex (sgx_c2c)
+    "sgx_fft2d_create": (_ST, [_sz, _sz, _i32, _i32, _P(_vp)]),
+    **_family("sgx_fft2d"),
+    "sgx_fft2d_forward": (_ST, [_vp, _vp, _sz, _vp, _i32, _vp]),
+    "sgx_fft2d_inverse": (_ST, [_vp, _vp, _sz, _vp, _i32, _vp]),
+    "sgx_fft2d_convolve": (_ST, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _i32, _vp]),
+    "sgx_fft2d_filter": (_ST, [_vp, _vp, _sz, _i32, _f64, _f64, _vp, _i32, _vp]),
+    "sgx_fft2d_reserve": (_ST, [_vp, _sz, _i32]),
+    "sgx_c2c_create": (_ST, [_sz, _i32, _i32, _P(_vp)]),
+    **_family("sgx_c2c", kernel_name=False, device=False),
+    "sgx_c2c_forward": (_ST, [_vp, _vp, _sz]),
+    "sgx_c2c_inverse": (_ST, [_vp, _vp, _sz]),
+    # MDCT (sgx_mdct)
+    "sgx_mdct_create": (_ST, [_sz, _sz, _i32, _f64, _P(_f64), _u32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_mdct", kernel_name=False),
+    "sgx_mdct_kernel_name": (_str, [_vp, _i32]),
+    "sgx_mdct_output_shape": (_ST, [_vp, _sz, _P(_sz), _P(_sz)]),
+    "sgx_mdct_inverse_length": (_ST, [_vp, _sz, _P(_sz)]),
+    "sgx_mdct_forward": (_ST, [_vp, _vp, _sz, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_mdct_inverse": (_ST, _EXEC),
+    "sgx_mdct_reserve": (_ST, _RESERVE),
+    "sgx_mdct_window": (_ST, [_vp, _P(_f64)]),
+    # binaural (sgx_binaural)
+    "sgx_binaural_create": (_ST, [_P(SgxParams), _P(SgxBinauralParams), _P(_vp)]),
+    **_family("sgx_binaural"),
+    "sgx_binaural_output_shape": (_ST, [_vp, _sz, _P(_sz), _P(_sz), _P(_sz)]),
+    "sgx_binaural_axes": (_ST, [_vp, _sz, _P(_f64), _P(_f64)]),
+    "sgx_binaural_execute": (_ST, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_binaural_histogram": (_ST, [_vp, _vp, _sz, _sz, _sz, _f64, _f64, _i32, _i32, _vp, _sz, _i32, _vp]),
+    "sgx_binaural_reserve": (_ST, _RESERVE),
+    # gammatone (sgx_gammatone)
+    "sgx_gammatone_create": (_ST, [_f64, _sz, _sz, _u32, _f64, _f64, _i32, _i32, _f64, _i32, _i32, _P(_vp)]),
+    **_family("sgx_gammatone"),
+    "sgx_gammatone_output_shape": (_ST, [_vp, _sz, _P(_sz), _P(_sz)]),
+    "sgx_gammatone_execute": (_ST, _EXEC),
+    "sgx_gammatone_center_frequencies": (_ST, [_vp, _P(_f64)]),
+    "sgx_gammatone_coefficients": (_ST, [_vp, _P(_f64)]),
+    "sgx_gammatone_reserve": (_ST, _RESERVE),
+    # FIR and deconvolution (sgx_fir, sgx_deconv)
+    "sgx_fir_create": (_ST, [_P(_f64), _sz, _sz, _sz, _i32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_fir", sizes=("fft_size", "step", "taps")),
+    "sgx_fir_process": (_ST, _EXEC),
+    "sgx_fir_convolve": (_ST, _EXEC),
+    "sgx_fir_reset": (_ST, [_vp, _vp]),
+    "sgx_fir_reserve": (_ST, _RESERVE),
+    "sgx_deconv_create": (_ST, [_sz, _sz, _f64, _i32, _i32, _P(_vp)]),
+    **_family("sgx_deconv", sizes=("output_length",), kernel_name=False),
+    "sgx_deconv_execute": (_ST, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_deconv_reserve": (_ST, _RESERVE),
+    # minimum phase (sgx_minphase)
+    "sgx_minphase_create": (_ST, [_sz, _sz, _sz, _i32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_minphase", sizes=("fft_size", "output_length", "taps")),
+    "sgx_minphase_execute": (_ST, [_vp, _vp, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_minphase_reserve": (_ST, [_vp, _sz, _i32]),
+    # streaming forward and inverse (sgx_stream, sgx_istream)
+    "sgx_stream_create": (_ST, [_P(SgxParams), _P(_vp)]),
+    **_family("sgx_stream", sizes=("pending", "frames_emitted", "n_bins", "allocations")),
+    "sgx_stream_step": (_ST, [_vp, _sz, _sz, _P(_sz), _P(_sz)]),
+    "sgx_stream_flush_frames": (_ST, [_vp, _P(_sz)]),
+    "sgx_stream_push": (_ST, _EXEC),
+    "sgx_stream_flush": (_ST, _FLUSH),
+    "sgx_stream_reset": (_ST, [_vp, _vp]),
+    "sgx_stream_reserve": (_ST, _RESERVE),
+    "sgx_istream_create": (_ST, [_P(SgxParams), _P(_vp)]),
+    **_family("sgx_istream", sizes=("frames_taken", "samples_emitted", "pending", "allocations")),
+    "sgx_istream_step": (_ST, [_vp, _sz, _sz, _P(_sz)]),
+    "sgx_istream_flush_samples": (_ST, [_vp, _P(_sz)]),
+    "sgx_istream_push": (_ST, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_istream_flush": (_ST, _FLUSH),
+    "sgx_istream_reset": (_ST, [_vp, _vp]),
+    "sgx_istream_reserve": (_ST, _RESERVE),
+    # sample-rate conversion (sgx_resample)
+    "sgx_resample_create": (_ST, [_i64, _i64, _i32, _f64, _i32, _f64, _i32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_resample", sizes=("up", "down", "taps_per_phase", "tile", "consumed", "emitted", "allocations")),
+    "sgx_resample_resample": (_ST, _EXEC),
+    "sgx_resample_process": (_ST, _EXEC),
+    "sgx_resample_flush": (_ST, _FLUSH),
+    "sgx_resample_reset": (_ST, [_vp, _vp]),
+    "sgx_resample_reserve": (_ST, _RESERVE),
+    "sgx_resample_step": (_ST, [_vp, _sz, _sz, _P(_sz), _P(_sz)]),
+    "sgx_resample_out_len": (_sz, [_vp, _sz]),
+    "sgx_resample_taps": (_ST, [_vp, _P(_f64)]),
+    "sgx_resample_phase_offsets": (_ST, [_vp, _P(_i64)]),
+    # Welch estimates (sgx_welch)
+    "sgx_welch_create": (_ST, [_P(SgxParams), _i32, _i32, _i32, _i32, _sz, _P(_vp)]),
+    **_family("sgx_welch", sizes=("n_bins", "allocations", "tile")),
+    "sgx_welch_n_segments": (_sz, [_vp, _sz]),
+    "sgx_welch_frequencies": (_ST, [_vp, _P(_f64)]),
+    "sgx_welch_window": (_ST, [_vp, _P(_f64)]),
+    "sgx_welch_scale": (_f64, [_vp]),
+    "sgx_welch_execute": (_ST, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _i32, _vp]),
+    "sgx_welch_reserve": (_ST, _RESERVE),
+}
+SYMBOLS = list(SIGNATURES)  # every symbol include/spectro_hip.h declares
 
 
 class SpectrogramError(Exception):
@@ -142,237 +259,9 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    vp, sz = C.c_void_p, C.c_size_t
-    L.sgx_plan_create.argtypes = [C.POINTER(SgxParams), C.POINTER(vp)]
-    L.sgx_plan_destroy.argtypes = [vp]
-    L.sgx_plan_destroy.restype = None
-    L.sgx_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_execute.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_execute_timed.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, C.c_int32, C.POINTER(C.c_float)]
-    L.sgx_axes.argtypes = [vp, sz, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.sgx_r2c.argtypes = [vp, vp, sz, vp, sz]
-    L.sgx_c2r.argtypes = [vp, vp, sz, vp, sz]
-    L.sgx_istft_length.argtypes = [vp, sz, C.POINTER(sz)]
-    L.sgx_istft.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_window.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_mel_weights.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
-    L.sgx_shard_range.argtypes = [sz, C.c_int32, C.c_int32, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_last_error.argtypes = [vp]
-    L.sgx_last_error.restype = C.c_char_p
-    L.sgx_last_create_error.restype = C.c_char_p
-    L.sgx_kernel_name.argtypes = [vp]
-    L.sgx_kernel_name.restype = C.c_char_p
-    L.sgx_istft_kernel_name.argtypes = [vp]
-    L.sgx_istft_kernel_name.restype = C.c_char_p
-    L.sgx_bank_stage_name.argtypes = [vp]
-    L.sgx_bank_stage_name.restype = C.c_char_p
-    L.sgx_abi_version.restype = C.c_int32
-    L.sgx_device_count.restype = C.c_int32
-    L.sgx_fft2d_create.argtypes = [sz, sz, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_fft2d_destroy.argtypes = [vp]
-    L.sgx_fft2d_destroy.restype = None
-    L.sgx_fft2d_forward.argtypes = [vp, vp, sz, vp, C.c_int32, vp]
-    L.sgx_fft2d_inverse.argtypes = [vp, vp, sz, vp, C.c_int32, vp]
-    L.sgx_fft2d_convolve.argtypes = [vp, vp, sz, vp, sz, sz, vp, C.c_int32, vp]
-    L.sgx_fft2d_filter.argtypes = [vp, vp, sz, C.c_int32, C.c_double, C.c_double, vp, C.c_int32, vp]
-    L.sgx_fft2d_last_error.argtypes = [vp]
-    L.sgx_fft2d_last_error.restype = C.c_char_p
-    L.sgx_fft2d_reserve.argtypes = [vp, sz, C.c_int32]
-    L.sgx_fft2d_device.argtypes = [vp]
-    L.sgx_fft2d_device.restype = C.c_int32
-    L.sgx_fft2d_kernel_name.argtypes = [vp]
-    L.sgx_fft2d_kernel_name.restype = C.c_char_p
-    L.sgx_reserve.argtypes = [vp, sz, sz, C.c_int32, C.c_int32]
-    L.sgx_plan_device.argtypes = [vp]
-    L.sgx_plan_device.restype = C.c_int32
-    L.sgx_last_dim_mismatch.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_c2c_create.argtypes = [sz, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_c2c_destroy.argtypes = [vp]
-    L.sgx_c2c_destroy.restype = None
-    L.sgx_c2c_forward.argtypes = [vp, vp, sz]
-    L.sgx_c2c_inverse.argtypes = [vp, vp, sz]
-    L.sgx_c2c_last_error.argtypes = [vp]
-    L.sgx_c2c_last_error.restype = C.c_char_p
-    L.sgx_comm_unique_id.argtypes = [vp]
-    L.sgx_comm_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_comm_adopt.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_comm_destroy.argtypes = [vp]
-    L.sgx_comm_destroy.restype = None
-    L.sgx_comm_last_error.argtypes = [vp]
-    L.sgx_comm_last_error.restype = C.c_char_p
-    L.sgx_gather.argtypes = [vp, vp, vp, sz, sz, C.c_int32, vp]
-    L.sgx_shard_execute.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
-    L.sgx_shard_execute_chunked.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, C.c_int32, vp]
-    L.sgx_membench.argtypes = [C.c_int32, sz, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
-    L.sgx_clock_probe.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
-    L.sgx_clock_probe.restype = C.c_int32
-    L.sgx_plan_create_cqt.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
-    L.sgx_plan_create_cqt_transform.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxCqtParams), C.POINTER(vp)]
-    L.sgx_cqt_set_route.argtypes = [vp, C.c_int32]
-    L.sgx_cqt_kernels.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.sgx_mdct_create.argtypes = [sz, sz, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_mdct_destroy.argtypes = [vp]
-    L.sgx_mdct_destroy.restype = None
-    L.sgx_mdct_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_mdct_inverse_length.argtypes = [vp, sz, C.POINTER(sz)]
-    L.sgx_mdct_forward.argtypes = [vp, vp, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_mdct_inverse.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_mdct_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_mdct_window.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_mdct_kernel_name.argtypes = [vp, C.c_int32]
-    L.sgx_mdct_kernel_name.restype = C.c_char_p
-    L.sgx_mdct_device.argtypes = [vp]
-    L.sgx_mdct_device.restype = C.c_int32
-    L.sgx_mdct_last_error.argtypes = [vp]
-    L.sgx_mdct_last_error.restype = C.c_char_p
-    L.sgx_binaural_create.argtypes = [C.POINTER(SgxParams), C.POINTER(SgxBinauralParams), C.POINTER(vp)]
-    L.sgx_binaural_destroy.argtypes = [vp]
-    L.sgx_binaural_destroy.restype = None
-    L.sgx_binaural_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_binaural_axes.argtypes = [vp, sz, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.sgx_binaural_execute.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_binaural_histogram.argtypes = [vp, vp, sz, sz, sz, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, sz, C.c_int32, vp]
-    L.sgx_binaural_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_binaural_kernel_name.argtypes = [vp]
-    L.sgx_binaural_kernel_name.restype = C.c_char_p
-    L.sgx_binaural_device.argtypes = [vp]
-    L.sgx_binaural_device.restype = C.c_int32
-    L.sgx_binaural_last_error.argtypes = [vp]
-    L.sgx_binaural_last_error.restype = C.c_char_p
-    L.sgx_gammatone_create.argtypes = [C.c_double, sz, sz, C.c_uint32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int32,
-                                       C.c_int32, C.POINTER(vp)]
-    L.sgx_gammatone_destroy.argtypes = [vp]
-    L.sgx_gammatone_destroy.restype = None
-    L.sgx_gammatone_output_shape.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_gammatone_execute.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_gammatone_center_frequencies.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_gammatone_coefficients.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_gammatone_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_gammatone_kernel_name.argtypes = [vp]
-    L.sgx_gammatone_kernel_name.restype = C.c_char_p
-    L.sgx_gammatone_device.argtypes = [vp]
-    L.sgx_gammatone_device.restype = C.c_int32
-    L.sgx_gammatone_last_error.argtypes = [vp]
-    L.sgx_gammatone_last_error.restype = C.c_char_p
-    L.sgx_fir_create.argtypes = [C.POINTER(C.c_double), sz, sz, sz, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_fir_destroy.argtypes = [vp]
-    L.sgx_fir_destroy.restype = None
-    L.sgx_fir_process.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_fir_convolve.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_fir_reset.argtypes = [vp, vp]
-    L.sgx_fir_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    for f in (L.sgx_fir_fft_size, L.sgx_fir_step, L.sgx_fir_taps, L.sgx_deconv_output_length):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_fir_kernel_name.argtypes = [vp]
-    L.sgx_fir_kernel_name.restype = C.c_char_p
-    L.sgx_fir_device.argtypes = [vp]
-    L.sgx_fir_device.restype = C.c_int32
-    L.sgx_fir_last_error.argtypes = [vp]
-    L.sgx_fir_last_error.restype = C.c_char_p
-    L.sgx_deconv_create.argtypes = [sz, sz, C.c_double, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_deconv_destroy.argtypes = [vp]
-    L.sgx_deconv_destroy.restype = None
-    L.sgx_deconv_execute.argtypes = [vp, vp, vp, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_deconv_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_deconv_device.argtypes = [vp]
-    L.sgx_deconv_device.restype = C.c_int32
-    L.sgx_deconv_last_error.argtypes = [vp]
-    L.sgx_deconv_last_error.restype = C.c_char_p
-    L.sgx_minphase_create.argtypes = [sz, sz, sz, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.sgx_minphase_destroy.argtypes = [vp]
-    L.sgx_minphase_destroy.restype = None
-    L.sgx_minphase_execute.argtypes = [vp, vp, sz, vp, sz, C.c_int32, vp]
-    L.sgx_minphase_reserve.argtypes = [vp, sz, C.c_int32]
-    for f in (L.sgx_minphase_fft_size, L.sgx_minphase_output_length, L.sgx_minphase_taps):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_minphase_kernel_name.argtypes = [vp]
-    L.sgx_minphase_kernel_name.restype = C.c_char_p
-    L.sgx_minphase_device.argtypes = [vp]
-    L.sgx_minphase_device.restype = C.c_int32
-    L.sgx_minphase_last_error.argtypes = [vp]
-    L.sgx_minphase_last_error.restype = C.c_char_p
-    L.sgx_stream_create.argtypes = [C.POINTER(SgxParams), C.POINTER(vp)]
-    L.sgx_stream_destroy.argtypes = [vp]
-    L.sgx_stream_destroy.restype = None
-    L.sgx_stream_step.argtypes = [vp, sz, sz, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_stream_flush_frames.argtypes = [vp, C.POINTER(sz)]
-    for f in (L.sgx_stream_pending, L.sgx_stream_frames_emitted, L.sgx_stream_n_bins, L.sgx_stream_allocations):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_stream_push.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_stream_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
-    L.sgx_stream_reset.argtypes = [vp, vp]
-    L.sgx_stream_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_stream_kernel_name.argtypes = [vp]
-    L.sgx_stream_kernel_name.restype = C.c_char_p
-    L.sgx_stream_device.argtypes = [vp]
-    L.sgx_stream_device.restype = C.c_int32
-    L.sgx_stream_last_error.argtypes = [vp]
-    L.sgx_stream_last_error.restype = C.c_char_p
-    L.sgx_istream_create.argtypes = [C.POINTER(SgxParams), C.POINTER(vp)]
-    L.sgx_istream_destroy.argtypes = [vp]
-    L.sgx_istream_destroy.restype = None
-    L.sgx_istream_step.argtypes = [vp, sz, sz, C.POINTER(sz)]
-    L.sgx_istream_flush_samples.argtypes = [vp, C.POINTER(sz)]
-    for f in (L.sgx_istream_frames_taken, L.sgx_istream_samples_emitted, L.sgx_istream_pending, L.sgx_istream_allocations):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_istream_push.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_istream_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
-    L.sgx_istream_reset.argtypes = [vp, vp]
-    L.sgx_istream_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_istream_kernel_name.argtypes = [vp]
-    L.sgx_istream_kernel_name.restype = C.c_char_p
-    L.sgx_istream_device.argtypes = [vp]
-    L.sgx_istream_device.restype = C.c_int32
-    L.sgx_istream_last_error.argtypes = [vp]
-    L.sgx_istream_last_error.restype = C.c_char_p
-    L.sgx_resample_create.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                      C.POINTER(vp)]
-    L.sgx_resample_destroy.argtypes = [vp]
-    L.sgx_resample_destroy.restype = None
-    L.sgx_resample_resample.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_resample_process.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_resample_flush.argtypes = [vp, vp, sz, C.c_int32, vp]
-    L.sgx_resample_reset.argtypes = [vp, vp]
-    L.sgx_resample_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_resample_step.argtypes = [vp, sz, sz, C.POINTER(sz), C.POINTER(sz)]
-    L.sgx_resample_out_len.argtypes = [vp, sz]
-    L.sgx_resample_out_len.restype = sz
-    for f in (L.sgx_resample_up, L.sgx_resample_down, L.sgx_resample_taps_per_phase, L.sgx_resample_tile, L.sgx_resample_consumed,
-              L.sgx_resample_emitted, L.sgx_resample_allocations):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_resample_taps.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_resample_phase_offsets.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.sgx_resample_kernel_name.argtypes = [vp]
-    L.sgx_resample_kernel_name.restype = C.c_char_p
-    L.sgx_resample_device.argtypes = [vp]
-    L.sgx_resample_device.restype = C.c_int32
-    L.sgx_resample_last_error.argtypes = [vp]
-    L.sgx_resample_last_error.restype = C.c_char_p
-    L.sgx_welch_create.argtypes = [C.POINTER(SgxParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, sz, C.POINTER(vp)]
-    L.sgx_welch_destroy.argtypes = [vp]
-    L.sgx_welch_destroy.restype = None
-    for f in (L.sgx_welch_n_bins, L.sgx_welch_allocations, L.sgx_welch_tile):
-        f.argtypes = [vp]
-        f.restype = sz
-    L.sgx_welch_n_segments.argtypes = [vp, sz]
-    L.sgx_welch_n_segments.restype = sz
-    L.sgx_welch_frequencies.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_welch_window.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_welch_scale.argtypes = [vp]
-    L.sgx_welch_scale.restype = C.c_double
-    L.sgx_welch_execute.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_int32, vp]
-    L.sgx_welch_reserve.argtypes = [vp, sz, sz, C.c_int32]
-    L.sgx_welch_kernel_name.argtypes = [vp]
-    L.sgx_welch_kernel_name.restype = C.c_char_p
-    L.sgx_welch_device.argtypes = [vp]
-    L.sgx_welch_device.restype = C.c_int32
-    L.sgx_welch_last_error.argtypes = [vp]
-    L.sgx_welch_last_error.restype = C.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -380,41 +269,6 @@ def lib() -> C.CDLL:
 def np_dtype(code: int):
     """numpy type of a dtype code (F32 / F64)."""
     return np.float32 if code == F32 else np.float64
-
-
-class NativeHandle:
-    """One opaque plan of a satellite family of the C ABI.  A subclass names the family's symbol prefix (`_prefix`, e.g. "sgx_mdct"),
-    sets `_lib` and `_dt` (the plan's dtype code) and passes its create call's status and handle to `_create`; every later status
-    goes through `_check`.  Creation errors are read from <prefix>_last_error(NULL), call errors from the plan."""
-
-    _prefix = ""
-    _h = None
-
-    def _last_error(self, handle) -> str:
-        return (getattr(self._lib, self._prefix + "_last_error")(handle) or b"").decode()
-
-    def _create(self, status: int, handle) -> None:
-        if status:
-            raise _ERR.get(status, InternalError)(self._last_error(None))
-        self._h = handle
-
-    def _check(self, status: int) -> None:
-        if status:
-            raise _ERR.get(status, InternalError)(self._last_error(self._h))
-
-    def __del__(self):
-        if self._h:
-            getattr(self._lib, self._prefix + "_destroy")(self._h)
-            self._h = None
-
-    @property
-    def _np(self):
-        return np_dtype(self._dt)
-
-    @property
-    def _tdt(self):
-        import torch
-        return torch.float32 if self._dt == F32 else torch.float64
 
 
 def raise_status(status: int, plan=None) -> None:
@@ -428,3 +282,7 @@ def raise_status(status: int, plan=None) -> None:
         if L.sgx_last_dim_mismatch(plan, C.byref(e), C.byref(g)) == SGX_OK:
             raise DimensionMismatchError(text, e.value, g.value)
     raise _ERR.get(status, InternalError)(text)
+
+
+# the base of the satellite plan families and the plan cache live in _handle.py, which reads the names above at call time
+from ._handle import NativeHandle, PlanCache, clear_plan_caches, current_device_key, custom_window, dtype_name  # noqa: E402,F401

@@ -24,11 +24,7 @@ def _stft_struct(sp: SpectrogramParams, dtype: int, device: int):
     p = _ffi.SgxParams()
     p.n_fft, p.hop_size, p.centre = st.n_fft, st.hop_size, int(st.centre)
     p.window_kind, p.window_param = st.window.kind, st.window.param
-    cw = None
-    if st.window.kind == _ffi.WIN_CUSTOM:
-        cw = np.ascontiguousarray(st.window.coefficients, np.float64)
-        p.custom_window = cw.ctypes.data_as(C.POINTER(C.c_double))
-        p.custom_window_len = cw.size
+    cw, p.custom_window, p.custom_window_len = _ffi.custom_window(st.window)
     p.sample_rate_hz = sp.sample_rate
     p.freq_scale, p.amp_scale = _ffi.FREQ_LINEAR, _ffi.AMP_COMPLEX
     p.dtype, p.device = dtype, device
@@ -139,15 +135,6 @@ class BinauralPlan(_ffi.NativeHandle):
         h = C.c_void_p()
         st = self._lib.sgx_binaural_create(C.byref(sp), C.byref(bp), C.byref(h))
         self._create(st, h)
-        self._device = int(self._lib.sgx_binaural_device(h))
-
-    @property
-    def device(self) -> int:
-        return self._device
-
-    @property
-    def dtype(self) -> str:
-        return "float32" if self._dt == _ffi.F32 else "float64"
 
     @property
     def kernel_name(self) -> str:
@@ -174,66 +161,42 @@ class BinauralPlan(_ffi.NativeHandle):
     # ---- host arrays ------------------------------------------------------------------------------------------------------
     def compute(self, left, right) -> np.ndarray:
         """1-D (n,) pair -> (n_bins, n_frames); 2-D (B, n) rows -> (B, n_bins, n_frames)."""
-        lf = np.ascontiguousarray(left, dtype=self._np)
-        rt = np.ascontiguousarray(right, dtype=self._np)
-        if lf.ndim not in (1, 2):
-            raise ValueError("left / right must be 1-D (n,) or 2-D (batch, n)")
-        if lf.shape != rt.shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: left has shape {lf.shape}, right {rt.shape}",
-                                              expected=lf.size, got=rt.size)
-        lb, rb = (lf[None], rt[None]) if lf.ndim == 1 else (lf, rt)
-        if lb.shape[0] == 0 or lb.shape[1] == 0:
+        shape, rshape = np.shape(left), np.shape(right)
+        if len(shape) in (1, 2) and shape != rshape:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: left has shape {shape}, right {rshape}",
+                                              expected=math.prod(shape), got=math.prod(rshape))
+        if len(shape) in (1, 2) and 0 in shape:
             raise _ffi.InvalidInputError("Invalid input: samples must be non-empty")
+        lb, squeezed = self._host_rows(left, "left / right (n,)")
+        rb, _ = self._host_rows(right, "left / right (n,)")
         _, nb, nf = self.output_shape(lb.shape[1])
         out = np.empty((lb.shape[0], nb, nf), self._np)
         self._check(self._lib.sgx_binaural_execute(self._h, lb.ctypes.data, rb.ctypes.data, lb.shape[0], lb.shape[1], lb.shape[1],
                                                    out.ctypes.data, out.size, _ffi.MEM_HOST, None))
-        return out[0] if lf.ndim == 1 else out
+        return out[0] if squeezed else out
 
     def histogram(self, values, num_bins: int, lo: float, hi: float, exponent: int = 1, normalize: bool = False) -> np.ndarray:
         """Per-frame histograms of maps (n_bins, n_frames) or (B, n_bins, n_frames) -> (num_bins, n_frames) / (B, num_bins, n_frames) f64."""
-        v = np.ascontiguousarray(values, dtype=self._np)
-        if v.ndim not in (2, 3):
-            raise ValueError("values must be 2-D (n_bins, n_frames) or 3-D (batch, n_bins, n_frames)")
-        vb = v[None] if v.ndim == 2 else v
+        vb, squeezed = self._host_rows(values, "values (n_bins, n_frames)", (2, 3))
         _, nb, _ = self.output_shape(self.params.spectrogram_params.stft.n_fft)
         if vb.shape[1] != nb:
             raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {nb} rows, got {vb.shape[1]}", expected=nb, got=vb.shape[1])
         out = np.empty((vb.shape[0], int(num_bins), vb.shape[2]), np.float64)
         self._check(self._lib.sgx_binaural_histogram(self._h, vb.ctypes.data, vb.shape[0], vb.shape[2], int(num_bins), float(lo), float(hi),
                                                      int(exponent), int(bool(normalize)), out.ctypes.data, out.size, _ffi.MEM_HOST, None))
-        return out[0] if v.ndim == 2 else out
+        return out[0] if squeezed else out
 
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
-    def _tensor(self, t, what: str, ndim: int):
-        import torch
-        tdt = self._tdt
-        if not t.is_cuda or t.device.index != self._device:
-            raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-        if t.dtype != tdt or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous tensor of the plan's dtype")
-        if t.dim() != ndim or t.shape[0] == 0:
-            raise ValueError(f"{what} must be {ndim}-D with batch > 0, got shape {tuple(t.shape)}")
-        return tdt
-
     def compute_torch(self, left, right, out=None):
         """(B, n) device tensors -> (B, n_bins, n_frames), asynchronous on the current stream."""
-        import torch
-        tdt = self._tensor(left, "left", 2)
-        self._tensor(right, "right", 2)
+        self._check_tensor(left, "left", 2)
+        self._check_tensor(right, "right", 2)
         if tuple(left.shape) != tuple(right.shape):
             raise _ffi.DimensionMismatchError(f"Dimension mismatch: left has shape {tuple(left.shape)}, right {tuple(right.shape)}")
         b, n = left.shape
-        _, nb, nf = self.output_shape(n)
-        if out is None:
-            out = torch.empty((b, nb, nf), dtype=tdt, device=left.device)
-        else:
-            self._tensor(out, "out", 3)
-            if tuple(out.shape) != (b, nb, nf):
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, nb, nf)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(left.device).cuda_stream
+        out = self._out_tensor(out, (b,) + self.output_shape(n)[1:], left.device)
         self._check(self._lib.sgx_binaural_execute(self._h, left.data_ptr(), right.data_ptr(), b, n, n, out.data_ptr(), out.numel(),
-                                                   _ffi.MEM_DEVICE, C.c_void_p(s)))
+                                                   _ffi.MEM_DEVICE, self._stream()))
         return out
 
 
@@ -334,26 +297,13 @@ class IlrSpectrogram(_BinauralSpectrogram):
 
 
 # ---- one-shot functions with a plan cache (cleared by clear_fft_plan_cache) ---------------------------------------------------
-_BIN_CACHE = {}
-_BIN_CACHE_MAX = 16
+_BIN_CACHE = _ffi.PlanCache()
 
 
 def _plan(params, dtype) -> BinauralPlan:
     from .functions import _key
-    import torch
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    key = (_key(params), parse_dtype(dtype), dev)
-    plan = _BIN_CACHE.pop(key, None)
-    if plan is None:
-        plan = BinauralPlan(params, dtype)
-        while len(_BIN_CACHE) >= _BIN_CACHE_MAX:
-            _BIN_CACHE.pop(next(iter(_BIN_CACHE)))
-    _BIN_CACHE[key] = plan  # most recently used last
-    return plan
-
-
-def clear_binaural_plan_cache() -> None:
-    _BIN_CACHE.clear()
+    key = (_key(params), parse_dtype(dtype), _ffi.current_device_key())
+    return _BIN_CACHE.get(key, lambda: BinauralPlan(params, dtype))
 
 
 def _pair(audio):

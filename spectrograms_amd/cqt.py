@@ -109,30 +109,18 @@ class CqtTransformPlan(Plan):
 
 
 # ---- one-shot function with a plan cache (cleared by clear_fft_plan_cache) ------------------------------------------------------
-_CQT_CACHE = {}
-_CQT_CACHE_MAX = 16
+_CQT_CACHE = _ffi.PlanCache()
 
 
 def transform_plan(sample_rate, kernel_length, hop_size, cqt_params, amp, db, dtype, device=_ffi.DEVICE_CURRENT) -> CqtTransformPlan:
     """Cached CqtTransformPlan on `device` (default: the current one), by value."""
     from .functions import _key
     from .params import parse_dtype
-    import torch
     dev = int(device)
     if dev == _ffi.DEVICE_CURRENT:
-        dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
+        dev = _ffi.current_device_key()
     key = (float(sample_rate), int(kernel_length), int(hop_size), _key(cqt_params), amp, _key(db), parse_dtype(dtype), dev)
-    plan = _CQT_CACHE.pop(key, None)
-    if plan is None:
-        plan = CqtTransformPlan(sample_rate, kernel_length, hop_size, cqt_params, amp, db, dtype, device)
-        while len(_CQT_CACHE) >= _CQT_CACHE_MAX:
-            _CQT_CACHE.pop(next(iter(_CQT_CACHE)))
-    _CQT_CACHE[key] = plan  # most recently used last
-    return plan
-
-
-def clear_cqt_plan_cache() -> None:
-    _CQT_CACHE.clear()
+    return _CQT_CACHE.get(key, lambda: CqtTransformPlan(sample_rate, kernel_length, hop_size, cqt_params, amp, db, dtype, device))
 
 
 def cqt(samples, sample_rate: float, params: CqtParams, hop_size: int, dtype: Optional[str] = None,

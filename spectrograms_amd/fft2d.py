@@ -21,15 +21,9 @@ class Fft2dPlan(_ffi.NativeHandle):
         self._lib = _ffi.lib()
         self.nrows, self.ncols = int(nrows), int(ncols)
         self._dt = parse_dtype(dtype)
-        self._cnp = np.complex64 if self._dt == _ffi.F32 else np.complex128
         h = C.c_void_p()
         st = self._lib.sgx_fft2d_create(self.nrows, self.ncols, self._dt, device, C.byref(h))
         self._create(st, h)
-        self._device = int(self._lib.sgx_fft2d_device(h))
-
-    @property
-    def device(self) -> int:
-        return self._device
 
     @property
     def kernel_name(self) -> str:
@@ -41,15 +35,12 @@ class Fft2dPlan(_ffi.NativeHandle):
         """Pre-size the plan-owned intermediates so that later calls of up to `batch` images do not allocate."""
         self._check(self._lib.sgx_fft2d_reserve(self._h, int(batch), int(host_staging)))
 
-    def _device_images(self, t, what: str, shape_tail, tdt):
-        """A wrong shape, dtype, layout or device would make the kernels read or write out of bounds: check before the call."""
-        if not t.is_cuda or t.device.index != self._device:
-            raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-        if t.dtype != tdt or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous tensor of the plan's dtype")
-        if t.dim() != len(shape_tail) + 1 or tuple(t.shape[1:]) != tuple(shape_tail) or t.shape[0] == 0:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected (batch, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}",
-                                              tuple(shape_tail), tuple(t.shape[1:]))
+    def _device_images(self, t, what: str, tail, batch=None):
+        """A wrong shape, dtype, layout or device would make the kernels read or write out of bounds: check before the call.  `t` is
+        (batch, *tail) with `batch` images (None: any number > 0); -> its batch."""
+        b = batch or (t.shape[0] if t.dim() else 0) or 1
+        self._out_tensor(t, (b,) + tuple(tail), None, what=what)
+        return b
 
     def _images(self, a) -> np.ndarray:
         x = np.ascontiguousarray(a, dtype=self._np)
@@ -61,12 +52,12 @@ class Fft2dPlan(_ffi.NativeHandle):
 
     def forward(self, images) -> np.ndarray:
         x = self._images(images)
-        out = np.empty((x.shape[0], self.nrows, self.ncols // 2 + 1), self._cnp)
+        out = np.empty((x.shape[0], self.nrows, self.ncols // 2 + 1), self._cdt)
         self._check(self._lib.sgx_fft2d_forward(self._h, x.ctypes.data, x.shape[0], out.ctypes.data, _ffi.MEM_HOST, None))
         return out
 
     def inverse(self, spectra) -> np.ndarray:
-        s = np.ascontiguousarray(spectra, dtype=self._cnp)
+        s = np.ascontiguousarray(spectra, dtype=self._cdt)
         if s.ndim == 2:
             s = s[None]
         if s.ndim != 3 or s.shape[1] != self.nrows:
@@ -95,70 +86,35 @@ class Fft2dPlan(_ffi.NativeHandle):
         return out
 
     # device-resident batched entry points (torch CUDA tensors), used by the benchmarks
-    def forward_torch(self, x, out=None):
-        import torch
-        cdt = self._tdt
-        self._device_images(x, "images", (self.nrows, self.ncols), cdt)
-        b = x.shape[0]
+    def _torch(self, fn, x, what, tail, out, out_tail, *args):
+        """One device call `fn(plan, x, batch, *args, out, MEM_DEVICE, stream)` on (batch, *tail) images -> (batch, *out_tail)."""
+        b = self._device_images(x, what, tail)
         if out is None:
-            out = torch.empty((b, self.nrows, self.ncols // 2 + 1, 2), dtype=cdt, device=x.device)
+            out = self._out_tensor(None, (b,) + out_tail, x.device)
         else:
-            self._device_images(out, "out", (self.nrows, self.ncols // 2 + 1, 2), cdt)
-            if out.shape[0] != b:
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {b}, got {out.shape[0]}", b, out.shape[0])
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(self._lib.sgx_fft2d_forward(self._h, x.data_ptr(), b, out.data_ptr(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+            self._device_images(out, "out", out_tail, b)
+        self._check(fn(self._h, x.data_ptr(), b, *args, out.data_ptr(), _ffi.MEM_DEVICE, self._stream()))
         return out
+
+    def forward_torch(self, x, out=None):
+        """fft2d of [B, nrows, ncols] device images -> [B, nrows, ncols/2+1, 2] half spectra (interleaved re, im), device resident."""
+        return self._torch(self._lib.sgx_fft2d_forward, x, "images", (self.nrows, self.ncols), out, (self.nrows, self.ncols // 2 + 1, 2))
 
     def inverse_torch(self, spec, out=None):
         """ifft2d of [B, nrows, ncols/2+1, 2] half spectra (interleaved re, im) -> [B, nrows, ncols], device resident."""
-        import torch
-        tdt = self._tdt
-        self._device_images(spec, "spectra", (self.nrows, self.ncols // 2 + 1, 2), tdt)
-        b = spec.shape[0]
-        if out is None:
-            out = torch.empty((b, self.nrows, self.ncols), dtype=tdt, device=spec.device)
-        else:
-            self._device_images(out, "out", (self.nrows, self.ncols), tdt)
-            if out.shape[0] != b:
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {b}, got {out.shape[0]}", b, out.shape[0])
-        s = torch.cuda.current_stream(spec.device).cuda_stream
-        self._check(self._lib.sgx_fft2d_inverse(self._h, spec.data_ptr(), b, out.data_ptr(), _ffi.MEM_DEVICE, C.c_void_p(s)))
-        return out
+        return self._torch(self._lib.sgx_fft2d_inverse, spec, "spectra", (self.nrows, self.ncols // 2 + 1, 2), out, (self.nrows, self.ncols))
 
     def convolve_torch(self, x, kernel, out=None):
-        import torch
         k = np.ascontiguousarray(kernel, dtype=self._np)
         if k.ndim != 2:
             raise ValueError("kernel must be 2-D")
-        tdt = self._tdt
-        self._device_images(x, "images", (self.nrows, self.ncols), tdt)
-        if out is None:
-            out = torch.empty_like(x)
-        else:
-            self._device_images(out, "out", (self.nrows, self.ncols), tdt)
-            if out.shape[0] != x.shape[0]:
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {x.shape[0]}, got {out.shape[0]}", x.shape[0], out.shape[0])
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(self._lib.sgx_fft2d_convolve(self._h, x.data_ptr(), x.shape[0], k.ctypes.data, k.shape[0], k.shape[1],
-                                                 out.data_ptr(), _ffi.MEM_DEVICE, C.c_void_p(s)))
-        return out
+        shape = (self.nrows, self.ncols)
+        return self._torch(self._lib.sgx_fft2d_convolve, x, "images", shape, out, shape, k.ctypes.data, k.shape[0], k.shape[1])
 
     def filter_torch(self, x, kind: int, lo: float, hi: float = 0.0, out=None):
         """lowpass (0) / highpass (1) / bandpass (2) of [B, nrows, ncols] device images, device resident (src/image_ops.rs:301-430)."""
-        import torch
-        tdt = self._tdt
-        self._device_images(x, "images", (self.nrows, self.ncols), tdt)
-        if out is None:
-            out = torch.empty_like(x)
-        else:
-            self._device_images(out, "out", (self.nrows, self.ncols), tdt)
-            if out.shape[0] != x.shape[0]:
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {x.shape[0]}, got {out.shape[0]}", x.shape[0], out.shape[0])
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(self._lib.sgx_fft2d_filter(self._h, x.data_ptr(), x.shape[0], kind, float(lo), float(hi), out.data_ptr(),
-                                               _ffi.MEM_DEVICE, C.c_void_p(s)))
-        return out
+        shape = (self.nrows, self.ncols)
+        return self._torch(self._lib.sgx_fft2d_filter, x, "images", shape, out, shape, kind, float(lo), float(hi))
 
 
 class C2cPlan(_ffi.NativeHandle):
@@ -171,13 +127,12 @@ class C2cPlan(_ffi.NativeHandle):
         self._lib = _ffi.lib()
         self.n = int(n)
         self._dt = parse_dtype(dtype)
-        self._cnp = np.complex64 if self._dt == _ffi.F32 else np.complex128
         h = C.c_void_p()
         st = self._lib.sgx_c2c_create(self.n, self._dt, device, C.byref(h))
         self._create(st, h)
 
     def _run(self, fn, x) -> np.ndarray:
-        buf = np.array(x, dtype=self._cnp, copy=True).ravel()
+        buf = np.array(x, dtype=self._cdt, copy=True).ravel()
         st = fn(self._h, buf.ctypes.data, buf.size)
         if st == _ffi.SGX_DIM_MISMATCH:
             raise _ffi.DimensionMismatchError(self._last_error(self._h), self.n, buf.size)
@@ -195,8 +150,8 @@ class Fft2dPlanner:
     """Plan cache keyed by shape (src/fft2d.rs:491-657)."""
 
     def __init__(self, dtype=None):
-        self._plans = {}
-        self._dtype = "float32" if parse_dtype(dtype) == _ffi.F32 else "float64"  # fixed for the planner's lifetime
+        self._plans = _ffi.PlanCache()
+        self._dtype = _ffi.dtype_name(parse_dtype(dtype))  # fixed for the planner's lifetime
 
     @property
     def dtype(self) -> str:
@@ -205,9 +160,7 @@ class Fft2dPlanner:
     def _plan(self, shape, dtype) -> Fft2dPlan:
         dtype = self._dtype if dtype is None else dtype
         key = (int(shape[0]), int(shape[1]), parse_dtype(dtype))
-        if key not in self._plans:
-            self._plans[key] = Fft2dPlan(key[0], key[1], dtype)
-        return self._plans[key]
+        return self._plans.get(key, lambda: Fft2dPlan(key[0], key[1], dtype))
 
     def fft2d(self, data, dtype=None):
         a = _as2d(data)

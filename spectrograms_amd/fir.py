@@ -45,23 +45,16 @@ class FirPlan(_ffi.NativeHandle):
         st = self._lib.sgx_fir_create(h.ctypes.data_as(C.POINTER(C.c_double)) if h.size else None, taps, rows, self._block or 0,
                                       _ROUTES[route], self._dt, int(device), C.byref(ptr))
         self._create(st, ptr)
-        self._device = int(self._lib.sgx_fir_device(ptr))
 
     taps = property(lambda self: int(self._lib.sgx_fir_taps(self._h)))
     fft_size = property(lambda self: int(self._lib.sgx_fir_fft_size(self._h)), doc="the plan's segment length P")
     step = property(lambda self: int(self._lib.sgx_fir_step(self._h)), doc="S = P - (taps - 1): output samples per segment")
     block_size = property(lambda self: self._block, doc="the caller's block hint (None: none given)")
     kernel_name = property(lambda self: self._lib.sgx_fir_kernel_name(self._h).decode())
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
 
     def reset(self) -> None:
         """Zero history, and the row count of the next streaming call is free again."""
-        s = None
-        if self._device >= 0:
-            import torch
-            s = C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
-        self._check(self._lib.sgx_fir_reset(self._h, s))
+        self._check(self._lib.sgx_fir_reset(self._h, self._stream()))
 
     def reserve(self, batch: int, n_samples: int, host_staging: bool = True) -> None:
         """Pre-size the history and the plan-owned scratch so that calls of up to `batch` rows of `n_samples` samples do not allocate."""
@@ -69,15 +62,10 @@ class FirPlan(_ffi.NativeHandle):
 
     # ---- host arrays ------------------------------------------------------------------------------------------------------
     def _host(self, x, fn, extra):
-        a = np.ascontiguousarray(x, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("samples must be 1-D (n,) or 2-D (batch, n)")
-        xb = a[None] if a.ndim == 1 else a
-        if xb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
+        xb, squeezed = self._host_rows(x, "samples (n,)")
         out = np.empty((xb.shape[0], xb.shape[1] + extra), self._np)
         self._check(fn(self._h, xb.ctypes.data, xb.shape[0], xb.shape[1], xb.shape[1], out.ctypes.data, out.size, _ffi.MEM_HOST, None))
-        return out[0] if a.ndim == 1 else out
+        return out[0] if squeezed else out
 
     def process(self, x) -> np.ndarray:
         """Streaming: (n,) or (batch, n) -> the same shape; the rows' history moves on."""
@@ -88,34 +76,20 @@ class FirPlan(_ffi.NativeHandle):
         return self._host(x, self._lib.sgx_fir_convolve, self.taps - 1)
 
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
-    def _torch(self, x, out, fn, extra):
-        import torch
-        tdt = self._tdt
-        for t, what in ((x, "samples"), (out, "out")):
-            if t is None:
-                continue
-            if not t.is_cuda or t.device.index != self._device:
-                raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-            if t.dtype != tdt or not t.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous tensor of the plan's dtype")
-            if t.dim() != 2 or t.shape[0] == 0:
-                raise ValueError(f"{what} must be 2-D with batch > 0, got shape {tuple(t.shape)}")
+    def _torch(self, x, out, fn, full):
+        self._check_tensor(x, "samples", 2)
         b, n = x.shape
-        if out is None:
-            out = torch.empty((b, n + extra), dtype=tdt, device=x.device)
-        elif tuple(out.shape) != (b, n + extra):
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, n + extra)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(fn(self._h, x.data_ptr(), b, n, n, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        out = self._out_tensor(out, (b, n + self.taps - 1 if full else n), x.device)
+        self._check(fn(self._h, x.data_ptr(), b, n, n, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, self._stream()))
         return out
 
     def process_torch(self, x, out=None):
         """(batch, n) device tensor -> (batch, n), asynchronous on the current stream.  `out` must not overlap `x`."""
-        return self._torch(x, out, self._lib.sgx_fir_process, 0)
+        return self._torch(x, out, self._lib.sgx_fir_process, False)
 
     def convolve_torch(self, x, out=None):
         """(batch, n) device tensor -> (batch, n + taps - 1), asynchronous on the current stream."""
-        return self._torch(x, out, self._lib.sgx_fir_convolve, self.taps - 1)
+        return self._torch(x, out, self._lib.sgx_fir_convolve, True)
 
 
 class OverlapSaveConvolver(FirPlan):
@@ -149,47 +123,36 @@ class DeconvPlan(_ffi.NativeHandle):
         ptr = C.c_void_p()
         st = self._lib.sgx_deconv_create(self.n_len, self.d_len, float(regularization), self._dt, int(device), C.byref(ptr))
         self._create(st, ptr)
-        self._device = int(self._lib.sgx_deconv_device(ptr))
 
     output_length = property(lambda self: int(self._lib.sgx_deconv_output_length(self._h)))
-    device = property(lambda self: self._device)
 
     def reserve(self, batch: int, den_rows: int = 1, host_staging: bool = True) -> None:
         self._check(self._lib.sgx_deconv_reserve(self._h, int(batch), int(den_rows), int(host_staging)))
 
     def execute(self, numerator, denominator) -> np.ndarray:
         """numerator (n_len,) or (batch, n_len); denominator (d_len,) or (batch, d_len) -> (..., output_length)."""
-        num = np.ascontiguousarray(numerator, dtype=self._np)
-        den = np.ascontiguousarray(denominator, dtype=self._np)
-        if num.ndim not in (1, 2) or den.ndim not in (1, 2):
-            raise ValueError("numerator and denominator must be 1-D or 2-D (batch, n)")
-        nb, db = (num[None] if num.ndim == 1 else num), (den[None] if den.ndim == 1 else den)
-        if nb.shape[1] != self.n_len or db.shape[1] != self.d_len:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(self.n_len, self.d_len)}, got {(nb.shape[1], db.shape[1])}")
-        if nb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
-        if den.ndim == 2 and db.shape[0] != nb.shape[0]:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {nb.shape[0]}, got {db.shape[0]}", nb.shape[0], db.shape[0])
+        nshape, dshape = np.shape(numerator), np.shape(denominator)
+        if len(nshape) in (1, 2) and len(dshape) in (1, 2) and (nshape[-1], dshape[-1]) != (self.n_len, self.d_len):
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(self.n_len, self.d_len)}, got {(nshape[-1], dshape[-1])}")
+        nb, squeezed = self._host_rows(numerator, "numerator (n,)")
+        if len(dshape) == 2 and dshape[0] != nb.shape[0]:
+            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {nb.shape[0]}, got {dshape[0]}", nb.shape[0], dshape[0])
+        db, _ = self._host_rows(denominator, "denominator (n,)")
         out = np.empty((nb.shape[0], self.output_length), self._np)
         self._check(self._lib.sgx_deconv_execute(self._h, nb.ctypes.data, db.ctypes.data, nb.shape[0], db.shape[0], out.ctypes.data,
                                                  out.size, _ffi.MEM_HOST, None))
-        return out[0] if num.ndim == 1 else out
+        return out[0] if squeezed else out
 
     def execute_torch(self, numerator, denominator, out=None):
         """(batch, n_len) and (1 or batch, d_len) device tensors -> (batch, output_length), asynchronous on the current stream."""
-        import torch
-        tdt = self._tdt
         for t, what, w in ((numerator, "numerator", self.n_len), (denominator, "denominator", self.d_len)):
-            if not t.is_cuda or t.device.index != self._device:
-                raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-            if t.dtype != tdt or not t.is_contiguous() or t.dim() != 2 or t.shape[0] == 0 or t.shape[1] != w:
+            self._check_tensor(t, what, 2)
+            if t.shape[1] != w:
                 raise ValueError(f"{what} must be a contiguous (rows, {w}) tensor of the plan's dtype")
         b = numerator.shape[0]
-        if out is None:
-            out = torch.empty((b, self.output_length), dtype=tdt, device=numerator.device)
-        s = torch.cuda.current_stream(numerator.device).cuda_stream
+        out = self._out_tensor(out, (b, self.output_length), numerator.device)
         self._check(self._lib.sgx_deconv_execute(self._h, numerator.data_ptr(), denominator.data_ptr(), b, denominator.shape[0],
-                                                 out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+                                                 out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, self._stream()))
         return out
 
 

@@ -11,8 +11,7 @@ from .planner import Plan as _Plan
 # The reference caches FFT plans process-wide (src/fft_backend.rs:946-1076; clear_fft_plan_cache / fft_plan_cache_info in the
 # Python module).  Here a "plan" also owns its device tables (window, twiddles, filterbank), so a one-shot compute_* call that
 # repeats earlier parameters reuses the whole plan instead of rebuilding and re-uploading them.  Least-recently-used, bounded.
-_PLAN_CACHE = {}
-_PLAN_CACHE_MAX = 32
+_PLAN_CACHE = _ffi.PlanCache(32)
 
 
 def _key(obj):
@@ -45,31 +44,13 @@ def _key(obj):
 def Plan(params, amp, mapping, db, dtype, mfcc=None, inverse=False):
     """Cached constructor used by every one-shot function below (same arguments as planner.Plan)."""
     from .params import parse_dtype
-    import torch
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    key = (_key(params), amp, _key(mapping), _key(db), parse_dtype(dtype), _key(mfcc), bool(inverse), dev)
-    plan = _PLAN_CACHE.pop(key, None)
-    if plan is None:
-        plan = _Plan(params, amp, mapping, db, dtype, mfcc=mfcc)
-        while len(_PLAN_CACHE) >= _PLAN_CACHE_MAX:
-            _PLAN_CACHE.pop(next(iter(_PLAN_CACHE)))
-    _PLAN_CACHE[key] = plan  # most recently used last
-    return plan
+    key = (_key(params), amp, _key(mapping), _key(db), parse_dtype(dtype), _key(mfcc), bool(inverse), _ffi.current_device_key())
+    return _PLAN_CACHE.get(key, lambda: _Plan(params, amp, mapping, db, dtype, mfcc=mfcc))
 
 
 def clear_fft_plan_cache() -> None:
-    """Drop every cached plan (and its device tables), the MDCT plans of mdct / imdct, the binaural, the gammatone, the cqt() and the Welch plans included."""
-    from .binaural import clear_binaural_plan_cache
-    from .cqt import clear_cqt_plan_cache
-    from .gammatone import clear_gammatone_plan_cache
-    from .mdct import clear_mdct_plan_cache
-    from .welch import clear_welch_plan_cache
-    _PLAN_CACHE.clear()
-    clear_welch_plan_cache()
-    clear_mdct_plan_cache()
-    clear_binaural_plan_cache()
-    clear_gammatone_plan_cache()
-    clear_cqt_plan_cache()
+    """Drop every cached plan (and its device tables) of every family: each plan cache registers itself when it is made."""
+    _ffi.clear_plan_caches()
 
 
 def fft_plan_cache_info():

@@ -41,11 +41,6 @@ class GammatonePlan(_ffi.NativeHandle):
                                             1 if erb_params.spacing == "apple_tr35" else 0, int(floor is not None),
                                             0.0 if floor is None else float(floor), self._dt, int(device), C.byref(h))
         self._create(st, h)
-        self._device = int(self._lib.sgx_gammatone_device(h))
-
-    @property
-    def device(self) -> int:
-        return self._device
 
     @property
     def n_bands(self) -> int:
@@ -104,51 +99,22 @@ class GammatonePlan(_ffi.NativeHandle):
     def compute_torch(self, x, out=None):
         """(batch, n) device tensor (unit stride along n, any row stride >= n) -> (batch, n_bands, n_frames), asynchronous on the
         current stream."""
-        import torch
-        tdt = self._tdt
-        if not x.is_cuda or x.device.index != self._device:
-            raise ValueError(f"samples is on {x.device}, the plan is bound to cuda:{self._device}")
-        if x.dtype != tdt or x.dim() != 2 or x.shape[0] == 0:
-            raise ValueError(f"samples must be a 2-D tensor of the plan's dtype with batch > 0, got {x.dtype} {tuple(x.shape)}")
+        stride = self._check_tensor(x, "samples", 2, rows_may_stride=True)
         b, n = x.shape
-        if x.stride(1) != 1 or (b > 1 and x.stride(0) < n):
-            raise ValueError("samples must have unit stride along the samples and a row stride >= n_samples")
-        nb, nf = self.output_shape(n)
-        if out is None:
-            out = torch.empty((b, nb, nf), dtype=tdt, device=x.device)
-        else:
-            if not out.is_cuda or out.device != x.device or out.dtype != tdt or not out.is_contiguous():
-                raise ValueError("out must be a contiguous tensor of the plan's dtype on the plan's device")
-            if tuple(out.shape) != (b, nb, nf):
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, nb, nf)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        stride = x.stride(0) if b > 1 else n
+        out = self._out_tensor(out, (b,) + self.output_shape(n), x.device)
         self._check(self._lib.sgx_gammatone_execute(self._h, x.data_ptr(), b, n, stride, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE,
-                                                    C.c_void_p(s)))
+                                                    self._stream()))
         return out
 
 
 # ---- one-shot functions with a plan cache (cleared by clear_fft_plan_cache) ---------------------------------------------------
-_GT_CACHE = {}
-_GT_CACHE_MAX = 16
+_GT_CACHE = _ffi.PlanCache()
 
 
 def _plan(sample_rate, frame_size, hop_size, erb_params, dtype) -> GammatonePlan:
     from .functions import _key
-    import torch
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    key = (float(sample_rate), int(frame_size), int(hop_size), _key(erb_params), parse_dtype(dtype), dev)
-    plan = _GT_CACHE.pop(key, None)
-    if plan is None:
-        plan = GammatonePlan(sample_rate, frame_size, hop_size, erb_params, dtype)
-        while len(_GT_CACHE) >= _GT_CACHE_MAX:
-            _GT_CACHE.pop(next(iter(_GT_CACHE)))
-    _GT_CACHE[key] = plan  # most recently used last
-    return plan
-
-
-def clear_gammatone_plan_cache() -> None:
-    _GT_CACHE.clear()
+    key = (float(sample_rate), int(frame_size), int(hop_size), _key(erb_params), parse_dtype(dtype), _ffi.current_device_key())
+    return _GT_CACHE.get(key, lambda: GammatonePlan(sample_rate, frame_size, hop_size, erb_params, dtype))
 
 
 def gammatone_iir_spectrogram(samples, sample_rate: float, frame_size: int, hop_size: int, erb_params: ErbParams,

@@ -78,19 +78,11 @@ class MdctPlan(_ffi.NativeHandle):
         self.params = params
         self._dt = parse_dtype(dtype)
         w = params.window
-        cw, clen = None, 0
-        if w.kind == _ffi.WIN_CUSTOM:
-            self._cw = np.ascontiguousarray(w.coefficients, dtype=np.float64)
-            cw, clen = self._cw.ctypes.data_as(C.POINTER(C.c_double)), self._cw.size
+        self._cw, cw, clen = _ffi.custom_window(w)
         h = C.c_void_p()
         st = self._lib.sgx_mdct_create(params.window_size, params.hop_size, w.kind, w.param, cw, clen, self._dt, int(device),
                                        C.byref(h))
         self._create(st, h)
-        self._device = int(self._lib.sgx_mdct_device(h))
-
-    @property
-    def device(self) -> int:
-        return self._device
 
     @property
     def n_coefficients(self) -> int:
@@ -122,17 +114,12 @@ class MdctPlan(_ffi.NativeHandle):
     # ---- host arrays ------------------------------------------------------------------------------------------------------
     def forward(self, x) -> np.ndarray:
         """1-D (n,) -> (N, n_frames); 2-D (batch, n) -> (batch, N, n_frames)."""
-        a = np.ascontiguousarray(x, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("samples must be 1-D (n,) or 2-D (batch, n)")
-        xb = a[None] if a.ndim == 1 else a
-        if xb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
+        xb, squeezed = self._host_rows(x, "samples (n,)")
         nc, nf = self.output_shape(xb.shape[1])
         out = np.empty((xb.shape[0], nc, nf), self._np)
         self._check(self._lib.sgx_mdct_forward(self._h, xb.ctypes.data, xb.shape[0], xb.shape[1], out.ctypes.data, out.size,
                                                _ffi.MEM_HOST, None))
-        return out[0] if a.ndim == 1 else out
+        return out[0] if squeezed else out
 
     def _rows(self, r: int) -> None:
         n = self.params.n_coefficients
@@ -141,12 +128,7 @@ class MdctPlan(_ffi.NativeHandle):
 
     def inverse(self, c, original_length: Optional[int] = None) -> np.ndarray:
         """2-D (N, n_frames) -> 1-D; 3-D (batch, N, n_frames) -> (batch, length)."""
-        a = np.ascontiguousarray(c, dtype=self._np)
-        if a.ndim not in (2, 3):
-            raise ValueError("coefficients must be 2-D (N, n_frames) or 3-D (batch, N, n_frames)")
-        cb = a[None] if a.ndim == 2 else a
-        if cb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
+        cb, squeezed = self._host_rows(c, "coefficients (N, n_frames)", (2, 3))
         self._rows(cb.shape[1])
         length = self.inverse_length(cb.shape[2])
         out = np.empty((cb.shape[0], length), self._np)
@@ -155,78 +137,37 @@ class MdctPlan(_ffi.NativeHandle):
                                                    out.size, _ffi.MEM_HOST, None))
         if original_length is not None:  # Vec::truncate: a larger value keeps the length
             out = out[:, :int(original_length)]
-        return out[0] if a.ndim == 2 else out
+        return out[0] if squeezed else out
 
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
-    def _tensor(self, t, what: str, ndim: int):
-        import torch
-        tdt = self._tdt
-        if not t.is_cuda or t.device.index != self._device:
-            raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-        if t.dtype != tdt or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous tensor of the plan's dtype")
-        if t.dim() != ndim or t.shape[0] == 0:
-            raise ValueError(f"{what} must be {ndim}-D with batch > 0, got shape {tuple(t.shape)}")
-        return tdt
-
     def forward_torch(self, x, out=None):
         """(batch, n) device tensor -> (batch, N, n_frames), asynchronous on the current stream."""
-        import torch
-        tdt = self._tensor(x, "samples", 2)
+        self._check_tensor(x, "samples", 2)
         b, n = x.shape
-        nc, nf = self.output_shape(n)
-        if out is None:
-            out = torch.empty((b, nc, nf), dtype=tdt, device=x.device)
-        else:
-            self._tensor(out, "out", 3)
-            if tuple(out.shape) != (b, nc, nf):
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, nc, nf)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(self._lib.sgx_mdct_forward(self._h, x.data_ptr(), b, n, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE,
-                                               C.c_void_p(s)))
+        out = self._out_tensor(out, (b,) + self.output_shape(n), x.device)
+        self._check(self._lib.sgx_mdct_forward(self._h, x.data_ptr(), b, n, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, self._stream()))
         return out
 
     def inverse_torch(self, c, out=None):
         """(batch, N, n_frames) device tensor -> (batch, hop n_frames + 2N - hop), asynchronous on the current stream."""
-        import torch
-        tdt = self._tensor(c, "coefficients", 3)
+        self._check_tensor(c, "coefficients", 3)
         b, r, nf = c.shape
         self._rows(r)
-        length = self.inverse_length(nf)
-        if out is None:
-            out = torch.empty((b, length), dtype=tdt, device=c.device)
-        else:
-            self._tensor(out, "out", 2)
-            if tuple(out.shape) != (b, length):
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, length)}, got {tuple(out.shape)}")
-        if length:
-            s = torch.cuda.current_stream(c.device).cuda_stream
+        out = self._out_tensor(out, (b, self.inverse_length(nf)), c.device)
+        if out.numel():
             self._check(self._lib.sgx_mdct_inverse(self._h, c.data_ptr(), b, r, nf, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE,
-                                                   C.c_void_p(s)))
+                                                   self._stream()))
         return out
 
 
 # ---- one-shot functions with a plan cache (cleared by clear_fft_plan_cache) ---------------------------------------------------
-_MDCT_CACHE = {}
-_MDCT_CACHE_MAX = 16
+_MDCT_CACHE = _ffi.PlanCache()
 
 
 def _plan(params: MdctParams, dtype) -> MdctPlan:
     from .functions import _key
-    import torch
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    key = (_key(params), parse_dtype(dtype), dev)
-    plan = _MDCT_CACHE.pop(key, None)
-    if plan is None:
-        plan = MdctPlan(params, dtype)
-        while len(_MDCT_CACHE) >= _MDCT_CACHE_MAX:
-            _MDCT_CACHE.pop(next(iter(_MDCT_CACHE)))
-    _MDCT_CACHE[key] = plan  # most recently used last
-    return plan
-
-
-def clear_mdct_plan_cache() -> None:
-    _MDCT_CACHE.clear()
+    key = (_key(params), parse_dtype(dtype), _ffi.current_device_key())
+    return _MDCT_CACHE.get(key, lambda: MdctPlan(params, dtype))
 
 
 def mdct(samples, params: MdctParams, dtype: Optional[str] = None) -> np.ndarray:

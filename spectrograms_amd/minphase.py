@@ -40,14 +40,11 @@ class MinPhasePlan(_ffi.NativeHandle):
         ptr = C.c_void_p()
         st = self._lib.sgx_minphase_create(taps, out_len, oversample, _ROUTES[route], self._dt, int(device), C.byref(ptr))
         self._create(st, ptr)
-        self._device = int(self._lib.sgx_minphase_device(ptr))
 
     taps = property(lambda self: int(self._lib.sgx_minphase_taps(self._h)))
     fft_size = property(lambda self: int(self._lib.sgx_minphase_fft_size(self._h)), doc="n = next_power_of_two(taps * max(oversample, 1))")
     output_length = property(lambda self: int(self._lib.sgx_minphase_output_length(self._h)), doc="min(out_len, fft_size)")
     kernel_name = property(lambda self: self._lib.sgx_minphase_kernel_name(self._h).decode())
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
 
     def reserve(self, batch: int, host_staging: bool = True) -> None:
         """Pre-size the plan-owned scratch so that calls of up to `batch` rows do not allocate."""
@@ -55,40 +52,21 @@ class MinPhasePlan(_ffi.NativeHandle):
 
     def execute(self, ir) -> np.ndarray:
         """(taps,) or (batch, taps) host array -> (output_length,) or (batch, output_length)."""
-        a = np.ascontiguousarray(ir, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("ir must be 1-D (taps,) or 2-D (batch, taps)")
-        rows = a[None] if a.ndim == 1 else a
-        if rows.shape[0] == 0:
-            raise ValueError("batch must be > 0")
+        rows, squeezed = self._host_rows(ir, "ir (taps,)")
         if rows.shape[1] != self.taps:
             raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {self.taps}, got {rows.shape[1]}", self.taps, rows.shape[1])
         out = np.empty((rows.shape[0], self.output_length), self._np)
         self._check(self._lib.sgx_minphase_execute(self._h, rows.ctypes.data, rows.shape[0], out.ctypes.data, out.size, _ffi.MEM_HOST, None))
-        return out[0] if a.ndim == 1 else out
+        return out[0] if squeezed else out
 
     def execute_torch(self, ir, out=None):
         """(batch, taps) device tensor -> (batch, output_length), asynchronous on the current stream.  `out` must not overlap `ir`."""
-        import torch
-        tdt = self._tdt
-        for t, what in ((ir, "ir"), (out, "out")):
-            if t is None:
-                continue
-            if not t.is_cuda or t.device.index != self._device:
-                raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-            if t.dtype != tdt or not t.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous tensor of the plan's dtype")
-            if t.dim() != 2 or t.shape[0] == 0:
-                raise ValueError(f"{what} must be 2-D with batch > 0, got shape {tuple(t.shape)}")
+        self._check_tensor(ir, "ir", 2)
         b = ir.shape[0]
         if ir.shape[1] != self.taps:
             raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {self.taps}, got {ir.shape[1]}", self.taps, ir.shape[1])
-        if out is None:
-            out = torch.empty((b, self.output_length), dtype=tdt, device=ir.device)
-        elif tuple(out.shape) != (b, self.output_length):
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, self.output_length)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(ir.device).cuda_stream
-        self._check(self._lib.sgx_minphase_execute(self._h, ir.data_ptr(), b, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        out = self._out_tensor(out, (b, self.output_length), ir.device)
+        self._check(self._lib.sgx_minphase_execute(self._h, ir.data_ptr(), b, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, self._stream()))
         return out
 
 

@@ -194,11 +194,7 @@ def flatten_params(params: SpectrogramParams, amp: int, mel=None, db: Optional[L
     p = _ffi.SgxParams()
     p.n_fft, p.hop_size, p.centre = st.n_fft, st.hop_size, int(st.centre)
     p.window_kind, p.window_param = st.window.kind, st.window.param
-    cw = None
-    if st.window.kind == _ffi.WIN_CUSTOM:
-        cw = np.ascontiguousarray(st.window.coefficients, np.float64)
-        p.custom_window = cw.ctypes.data_as(C.POINTER(C.c_double))
-        p.custom_window_len = cw.size
+    cw, p.custom_window, p.custom_window_len = _ffi.custom_window(st.window)
     p.sample_rate_hz = params.sample_rate
     cq = None
     if isinstance(mel, CqtParams):  # sgx_plan_create_cqt: the mapping's own parameters travel in sgx_cqt_params
@@ -264,9 +260,7 @@ class Plan:
             self._h = None
 
     # ---- queries
-    @property
-    def dtype(self) -> str:
-        return "float32" if self._dt == _ffi.F32 else "float64"
+    dtype = _ffi.NativeHandle.dtype
 
     @property
     def is_complex(self) -> bool:

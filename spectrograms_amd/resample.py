@@ -50,7 +50,6 @@ class ResamplePlan(_ffi.NativeHandle):
         st = self._lib.sgx_resample_create(self.orig_freq, self.new_freq, lpw, float(rolloff), _METHODS[resampling_method],
                                            _KAISER_BETA if beta is None else float(beta), _ROUTES[route], self._dt, int(device), C.byref(ptr))
         self._create(st, ptr)
-        self._device = int(self._lib.sgx_resample_device(ptr))
         self._rows = 0         # fixed by the first process(); reset() and flush() free it
         self._squeeze = False  # the blocks are 1-D: the outputs come back without the batch axis
         self._torch = None     # the device of the last processed tensor (None: NumPy blocks)
@@ -64,8 +63,6 @@ class ResamplePlan(_ffi.NativeHandle):
     allocations = property(lambda self: int(self._lib.sgx_resample_allocations(self._h)),
                            doc="how often the plan has allocated or replaced one of its own buffers (it stands still within what reserve() sized)")
     kernel_name = property(lambda self: self._lib.sgx_resample_kernel_name(self._h).decode())
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
 
     def taps(self) -> np.ndarray:
         """The (L, K) table c[p][k] as the plan's kernels read it: the T-valued coefficients, as float64."""
@@ -90,12 +87,6 @@ class ResamplePlan(_ffi.NativeHandle):
         self._check(self._lib.sgx_resample_step(self._h, int(consumed), int(n_samples), C.byref(m), C.byref(after)))
         return m.value, after.value
 
-    def _stream(self):
-        if self._device < 0:
-            return None
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
-
     def reset(self) -> None:
         """Zero history, nothing consumed, and the row count of the next `process` is free again."""
         self._check(self._lib.sgx_resample_reset(self._h, self._stream()))
@@ -106,18 +97,9 @@ class ResamplePlan(_ffi.NativeHandle):
         self._check(self._lib.sgx_resample_reserve(self._h, int(batch), int(max_block), int(host_staging)))
 
     # ---- host arrays ------------------------------------------------------------------------------------------------------
-    def _rows_of(self, x):
-        a = np.ascontiguousarray(x, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("samples must be 1-D (n,) or 2-D (batch, n)")
-        xb = a[None] if a.ndim == 1 else a
-        if xb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
-        return xb, a.ndim == 1
-
     def resample(self, x) -> np.ndarray:
         """Stateless: (n,) or (batch, n) -> (..., out_len(n)); the plan's history is not touched."""
-        xb, sq = self._rows_of(x)
+        xb, sq = self._host_rows(x, "samples (n,)")
         b, n = xb.shape
         out = np.empty((b, self.out_len(n)), self._np)
         self._check(self._lib.sgx_resample_resample(self._h, xb.ctypes.data, b, n, n, out.ctypes.data, out.size, _ffi.MEM_HOST, None))
@@ -125,7 +107,7 @@ class ResamplePlan(_ffi.NativeHandle):
 
     def process(self, x) -> np.ndarray:
         """Streaming: (n,) or (batch, n) new samples -> the `step(consumed, n)[0]` outputs per row that became complete (possibly none)."""
-        xb, sq = self._rows_of(x)
+        xb, sq = self._host_rows(x, "samples (n,)")
         b, n = xb.shape
         out = np.empty((b, self.step(self.consumed, n)[0] if n else 0), self._np)
         self._check(self._lib.sgx_resample_process(self._h, xb.ctypes.data, b, n, n, out.ctypes.data if out.size else None, out.size,
@@ -144,59 +126,30 @@ class ResamplePlan(_ffi.NativeHandle):
         return out[0] if sq else out
 
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
-    def _check_tensor(self, t, what, rows_may_stride=False):
-        """-> the row stride in elements.  Samples may be a slice `X[:, a:b]` of a resident tensor (unit inner stride)."""
-        if not t.is_cuda or t.device.index != self._device:
-            raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-        if t.dim() != 2 or t.shape[0] == 0:
-            raise ValueError(f"{what} must be 2-D with batch > 0, got shape {tuple(t.shape)}")
-        b, n = t.shape
-        stride = t.stride(0) if b > 1 else max(n, 1)
-        strided_ok = rows_may_stride and (n <= 1 or t.stride(1) == 1) and stride >= n
-        if t.dtype != self._tdt or not (t.is_contiguous() or strided_ok):
-            raise ValueError(f"{what} must be a tensor of the plan's dtype, contiguous" + (" or with unit inner stride" if rows_may_stride else ""))
-        return stride
-
-    def _out_torch(self, out, shape, device):
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=self._tdt, device=device)
-        self._check_tensor(out, "out")
-        if tuple(out.shape) != shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
-        return out
-
     def resample_torch(self, x, out=None):
         """(batch, n) device tensor -> (batch, out_len(n)), asynchronous on the current stream.  `out` must not overlap `x`."""
-        import torch
-        stride = self._check_tensor(x, "samples", True)
+        stride = self._check_tensor(x, "samples", 2, rows_may_stride=True)
         b, n = x.shape
-        out = self._out_torch(out, (b, self.out_len(n)), x.device)
-        s = torch.cuda.current_stream(x.device).cuda_stream
-        self._check(self._lib.sgx_resample_resample(self._h, x.data_ptr(), b, n, stride, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        out = self._out_tensor(out, (b, self.out_len(n)), x.device)
+        self._check(self._lib.sgx_resample_resample(self._h, x.data_ptr(), b, n, stride, out.data_ptr(), out.numel(), _ffi.MEM_DEVICE, self._stream()))
         return out
 
     def process_torch(self, x, out=None):
         """(batch, n) new samples on the device -> (batch, step(consumed, n)[0]), asynchronous on the current stream."""
-        import torch
-        stride = self._check_tensor(x, "samples", True)
+        stride = self._check_tensor(x, "samples", 2, rows_may_stride=True)
         b, n = x.shape
-        out = self._out_torch(out, (b, self.step(self.consumed, n)[0] if n else 0), x.device)
-        s = torch.cuda.current_stream(x.device).cuda_stream
+        out = self._out_tensor(out, (b, self.step(self.consumed, n)[0] if n else 0), x.device)
         self._check(self._lib.sgx_resample_process(self._h, x.data_ptr(), b, n, stride, out.data_ptr() if out.numel() else None, out.numel(),
-                                                   _ffi.MEM_DEVICE, C.c_void_p(s)))
+                                                   _ffi.MEM_DEVICE, self._stream()))
         self._rows, self._squeeze, self._torch = b, False, x.device
         return out
 
     def flush_torch(self, out=None):
         """(batch, m) on the device of the last `process_torch`, asynchronous on the current stream; then as after `reset`."""
-        import torch
         if self._torch is None:
             raise ValueError("flush_torch() follows process_torch()")
-        dev = self._torch
-        out = self._out_torch(out, (self._rows, self.step(self.consumed, 0)[0]), dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        self._check(self._lib.sgx_resample_flush(self._h, out.data_ptr() if out.numel() else None, out.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
+        out = self._out_tensor(out, (self._rows, self.step(self.consumed, 0)[0]), self._torch)
+        self._check(self._lib.sgx_resample_flush(self._h, out.data_ptr() if out.numel() else None, out.numel(), _ffi.MEM_DEVICE, self._stream()))
         self._rows, self._squeeze, self._torch = 0, False, None
         return out
 

@@ -36,7 +36,6 @@ class StreamingPlan(_ffi.NativeHandle):
         p.dtype, p.device = self._dt, int(device)
         ptr = C.c_void_p()
         self._create(self._lib.sgx_stream_create(C.byref(p), C.byref(ptr)), ptr)
-        self._device = int(self._lib.sgx_stream_device(ptr))
         self._rows = 0          # fixed by the first push; reset() frees it
         self._squeeze = False   # the pushes are 1-D: the frames come back without the batch axis
         self._torch = None      # the device of the last pushed tensor (None: NumPy pushes)
@@ -47,8 +46,6 @@ class StreamingPlan(_ffi.NativeHandle):
     kernel_name = property(lambda self: self._lib.sgx_stream_kernel_name(self._h).decode(), doc="kernel_name of the plan that runs the frames")
     allocations = property(lambda self: int(self._lib.sgx_stream_allocations(self._h)),
                            doc="how often the stream has allocated or replaced one of its own buffers (it stands still within what reserve() sized)")
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
     is_complex = property(lambda self: self._complex)
 
     def frames(self, n_samples: int) -> int:
@@ -78,33 +75,9 @@ class StreamingPlan(_ffi.NativeHandle):
         self._check(self._lib.sgx_stream_reserve(self._h, int(batch), int(max_block), int(host_staging)))
 
     # ---- calls ------------------------------------------------------------------------------------------------------------
-    def _cdt(self):
-        return (np.complex64 if self._dt == _ffi.F32 else np.complex128) if self._complex else self._np
-
-    def _tcdt(self):
-        import torch
-        return (torch.complex64 if self._dt == _ffi.F32 else torch.complex128) if self._complex else self._tdt
-
-    def _out_numpy(self, out, shape):
-        if out is None:
-            return np.empty(shape, self._cdt())
-        if tuple(out.shape) != shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
-        if out.dtype != self._cdt() or not out.flags.c_contiguous:
-            raise ValueError("out must be C-contiguous with the plan's dtype")
-        return out
-
-    def _out_torch(self, out, shape, device):
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=self._tcdt(), device=device)
-        if tuple(out.shape) != shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
-        if out.dtype != self._tcdt() or not out.is_contiguous():
-            raise ValueError("out must be a contiguous tensor of the plan's dtype")
-        if not out.is_cuda or out.device.index != self._device:
-            raise ValueError(f"out is on {out.device}, the plan is bound to cuda:{self._device}")
-        return out
+    def _out_types(self):
+        """(numpy, torch) dtype of the frames: complex for a complex plan."""
+        return (self._cdt, self._tcdt) if self._complex else (self._np, self._tdt)
 
     def _elems(self, shape) -> int:
         return int(np.prod(shape)) * (2 if self._complex else 1)
@@ -115,40 +88,28 @@ class StreamingPlan(_ffi.NativeHandle):
         there, asynchronous on `stream` / torch's current stream.  `out`, if given, has the shape and dtype of the return value."""
         if type(block).__module__.startswith("torch"):
             return self._push_torch(block, out, stream)
-        a = np.ascontiguousarray(block, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("block must be 1-D (n,) or 2-D (batch, n)")
-        xb = a[None] if a.ndim == 1 else a
+        xb, sq = self._host_rows(block, "block (n,)")
         b, c = xb.shape
-        if b == 0:
-            raise ValueError("batch must be > 0")
         shape = (b, self.n_bins, self.frames(c))
-        res = self._out_numpy(out.reshape(shape) if out is not None and a.ndim == 1 and out.ndim == 2 else out, shape)
+        res = self._out_array(out.reshape(shape) if out is not None and sq and out.ndim == 2 else out, shape, self._out_types()[0])
         self._check(self._lib.sgx_stream_push(self._h, xb.ctypes.data, b, c, c, res.ctypes.data if res.size else None,
                                               self._elems(shape), _ffi.MEM_HOST, None))
-        self._rows, self._squeeze, self._torch = b, a.ndim == 1, None
-        return res[0] if a.ndim == 1 else res
+        self._rows, self._squeeze, self._torch = b, sq, None
+        return res[0] if sq else res
 
     def _push_torch(self, x, out, stream):
-        import torch
         if x.dim() not in (1, 2):
             raise ValueError("block must be 1-D (n,) or 2-D (batch, n)")
-        xb = x[None] if x.dim() == 1 else x
-        if not xb.is_cuda or xb.dtype != self._tdt or xb.stride(1) != 1 and xb.shape[1] > 1:
-            raise ValueError("device path needs a CUDA tensor of the plan's dtype with unit inner stride")
-        if xb.device.index != self._device:
-            raise ValueError(f"block is on {xb.device}, the plan is bound to cuda:{self._device}")
+        sq = x.dim() == 1
+        xb = x[None] if sq else x
+        stride = self._check_tensor(xb, "block", 2, rows_may_stride=True)
         b, c = xb.shape
-        if b == 0:
-            raise ValueError("batch must be > 0")
         shape = (b, self.n_bins, self.frames(c))
-        res = self._out_torch(out.reshape(shape) if out is not None and x.dim() == 1 and out.dim() == 2 else out, shape, xb.device)
-        s = stream or torch.cuda.current_stream(xb.device).cuda_stream
-        stride = xb.stride(0) if b > 1 else max(c, 1)
+        res = self._out_tensor(out.reshape(shape) if out is not None and sq and out.dim() == 2 else out, shape, xb.device, self._out_types()[1])
         self._check(self._lib.sgx_stream_push(self._h, xb.data_ptr(), b, c, stride, res.data_ptr() if res.numel() else None,
-                                              self._elems(shape), _ffi.MEM_DEVICE, C.c_void_p(s)))
-        self._rows, self._squeeze, self._torch = b, x.dim() == 1, xb.device
-        return res[0] if x.dim() == 1 else res
+                                              self._elems(shape), _ffi.MEM_DEVICE, self._stream(stream)))
+        self._rows, self._squeeze, self._torch = b, sq, xb.device
+        return res[0] if sq else res
 
     def flush(self, out=None, stream: int = 0):
         """The frames the trailing padding completes, shaped as `push` returns them for the fixed batch (as a tensor on `stream` /
@@ -156,12 +117,10 @@ class StreamingPlan(_ffi.NativeHandle):
         shape = (max(self._rows, 1), self.n_bins, self.flush_frames())
         sq = self._squeeze or self._rows == 0
         if self._torch is not None:
-            import torch
-            res = self._out_torch(out.reshape(shape) if out is not None and sq and out.dim() == 2 else out, shape, self._torch)
-            s = stream or torch.cuda.current_stream(self._torch).cuda_stream
-            args = (res.data_ptr() if res.numel() else None, self._elems(shape), _ffi.MEM_DEVICE, C.c_void_p(s))
+            res = self._out_tensor(out.reshape(shape) if out is not None and sq and out.dim() == 2 else out, shape, self._torch, self._out_types()[1])
+            args = (res.data_ptr() if res.numel() else None, self._elems(shape), _ffi.MEM_DEVICE, self._stream(stream))
         else:
-            res = self._out_numpy(out.reshape(shape) if out is not None and sq and out.ndim == 2 else out, shape)
+            res = self._out_array(out.reshape(shape) if out is not None and sq and out.ndim == 2 else out, shape, self._out_types()[0])
             args = (res.ctypes.data if res.size else None, self._elems(shape), _ffi.MEM_HOST, None)
         self._check(self._lib.sgx_stream_flush(self._h, *args))
         return res[0] if sq else res
@@ -184,7 +143,6 @@ class StreamingInversePlan(_ffi.NativeHandle):
         p.dtype, p.device = self._dt, int(device)
         ptr = C.c_void_p()
         self._create(self._lib.sgx_istream_create(C.byref(p), C.byref(ptr)), ptr)
-        self._device = int(self._lib.sgx_istream_device(ptr))
         self._rows = 0          # fixed by the first push; reset() frees it
         self._squeeze = False   # the pushes are 2-D: the samples come back without the batch axis
         self._torch = None      # the device of the last pushed tensor (None: NumPy pushes)
@@ -197,8 +155,6 @@ class StreamingInversePlan(_ffi.NativeHandle):
                            doc='the rows\' route of the last call + "+stream_ola"; "" before any call')
     allocations = property(lambda self: int(self._lib.sgx_istream_allocations(self._h)),
                            doc="how often the stream has allocated or replaced one of its own buffers (it stands still within what reserve() sized)")
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
 
     def samples(self, f: int) -> int:
         """Samples per row a push of `f >= 1` frames would return now."""
@@ -225,30 +181,6 @@ class StreamingInversePlan(_ffi.NativeHandle):
         self._check(self._lib.sgx_istream_reserve(self._h, int(batch), int(max_frames), int(host_staging)))
 
     # ---- calls ------------------------------------------------------------------------------------------------------------
-    def _cdt(self):
-        return np.complex64 if self._dt == _ffi.F32 else np.complex128
-
-    def _out_numpy(self, out, shape):
-        if out is None:
-            return np.empty(shape, self._np)
-        if tuple(out.shape) != shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
-        if out.dtype != self._np or not out.flags.c_contiguous:
-            raise ValueError("out must be C-contiguous with the plan's dtype")
-        return out
-
-    def _out_torch(self, out, shape, device):
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=self._tdt, device=device)
-        if tuple(out.shape) != shape:
-            raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {shape}, got {tuple(out.shape)}", shape, tuple(out.shape))
-        if out.dtype != self._tdt or not out.is_contiguous():
-            raise ValueError("out must be a contiguous tensor of the plan's dtype")
-        if not out.is_cuda or out.device.index != self._device:
-            raise ValueError(f"out is on {out.device}, the plan is bound to cuda:{self._device}")
-        return out
-
     def push(self, frames, out=None, stream: int = 0):
         """(n_bins, f) or (B, n_bins, f) new complex frames -> the samples that became final, (m,) or (B, m) (m may be 0).  NumPy in ->
         NumPy out (stream-owned staging, synchronous); a torch tensor on the plan's device -> a tensor there, asynchronous on `stream`
@@ -256,43 +188,28 @@ class StreamingInversePlan(_ffi.NativeHandle):
         taken from the tensor).  `out`, if given, has the shape and dtype of the return value."""
         if type(frames).__module__.startswith("torch"):
             return self._push_torch(frames, out, stream)
-        a = np.ascontiguousarray(frames, dtype=self._cdt())
-        if a.ndim not in (2, 3):
-            raise ValueError("frames must be 2-D (n_bins, f) or 3-D (batch, n_bins, f)")
-        xb = a[None] if a.ndim == 2 else a
+        xb, sq = self._host_rows(frames, "frames (n_bins, f)", (2, 3), self._cdt)
         b, nb, f = xb.shape
-        if b == 0:
-            raise ValueError("batch must be > 0")
         shape = (b, self.samples(f) if f and nb == self._n_bins else 0)
-        res = self._out_numpy(out.reshape(shape) if out is not None and a.ndim == 2 and out.ndim == 1 else out, shape)
+        res = self._out_array(out.reshape(shape) if out is not None and sq and out.ndim == 1 else out, shape)
         self._check(self._lib.sgx_istream_push(self._h, xb.ctypes.data, b, nb, f, f, res.ctypes.data if res.size else None, res.size,
                                                _ffi.MEM_HOST, None))
-        self._rows, self._squeeze, self._torch = b, a.ndim == 2, None
-        return res[0] if a.ndim == 2 else res
+        self._rows, self._squeeze, self._torch = b, sq, None
+        return res[0] if sq else res
 
     def _push_torch(self, x, out, stream):
-        import torch
         if x.dim() not in (2, 3):
             raise ValueError("frames must be 2-D (n_bins, f) or 3-D (batch, n_bins, f)")
-        xb = x[None] if x.dim() == 2 else x
-        want = torch.complex64 if self._dt == _ffi.F32 else torch.complex128
+        sq = x.dim() == 2
+        xb = x[None] if sq else x
+        bin_stride = self._check_tensor(xb, "frames", 3, rows_may_stride=True, dtype=self._tcdt)
         b, nb, f = xb.shape
-        if not xb.is_cuda or xb.dtype != want or xb.stride(2) != 1 and f > 1:
-            raise ValueError("device path needs a CUDA tensor of the plan's complex dtype with unit inner stride")
-        if xb.device.index != self._device:
-            raise ValueError(f"frames are on {xb.device}, the plan is bound to cuda:{self._device}")
-        if b == 0:
-            raise ValueError("batch must be > 0")
-        bin_stride = xb.stride(1) if nb > 1 else max(f, 1)
-        if bin_stride < f or b > 1 and xb.stride(0) != nb * bin_stride:
-            raise ValueError("device path needs rows of (n_bins, bin_stride) with nothing between them (a slice along the frame axis)")
         shape = (b, self.samples(f) if f and nb == self._n_bins else 0)
-        res = self._out_torch(out.reshape(shape) if out is not None and x.dim() == 2 and out.dim() == 1 else out, shape, xb.device)
-        s = stream or torch.cuda.current_stream(xb.device).cuda_stream
+        res = self._out_tensor(out.reshape(shape) if out is not None and sq and out.dim() == 1 else out, shape, xb.device)
         self._check(self._lib.sgx_istream_push(self._h, xb.data_ptr(), b, nb, f, bin_stride, res.data_ptr() if res.numel() else None,
-                                               res.numel(), _ffi.MEM_DEVICE, C.c_void_p(s)))
-        self._rows, self._squeeze, self._torch = b, x.dim() == 2, xb.device
-        return res[0] if x.dim() == 2 else res
+                                               res.numel(), _ffi.MEM_DEVICE, self._stream(stream)))
+        self._rows, self._squeeze, self._torch = b, sq, xb.device
+        return res[0] if sq else res
 
     def flush(self, out=None, stream: int = 0):
         """The samples that were waiting for later frames, shaped as `push` returns them for the fixed batch (as a tensor on `stream` /
@@ -300,12 +217,10 @@ class StreamingInversePlan(_ffi.NativeHandle):
         shape = (max(self._rows, 1), self.flush_samples())
         sq = self._squeeze or self._rows == 0
         if self._torch is not None:
-            import torch
-            res = self._out_torch(out.reshape(shape) if out is not None and sq and out.dim() == 1 else out, shape, self._torch)
-            s = stream or torch.cuda.current_stream(self._torch).cuda_stream
-            args = (res.data_ptr() if res.numel() else None, res.numel(), _ffi.MEM_DEVICE, C.c_void_p(s))
+            res = self._out_tensor(out.reshape(shape) if out is not None and sq and out.dim() == 1 else out, shape, self._torch)
+            args = (res.data_ptr() if res.numel() else None, res.numel(), _ffi.MEM_DEVICE, self._stream(stream))
         else:
-            res = self._out_numpy(out.reshape(shape) if out is not None and sq and out.ndim == 1 else out, shape)
+            res = self._out_array(out.reshape(shape) if out is not None and sq and out.ndim == 1 else out, shape)
             args = (res.ctypes.data if res.size else None, res.size, _ffi.MEM_HOST, None)
         self._check(self._lib.sgx_istream_flush(self._h, *args))
         return res[0] if sq else res

@@ -81,11 +81,7 @@ class WelchPlan(_ffi.NativeHandle):
         p = _ffi.SgxParams()
         p.n_fft, p.hop_size, p.centre = params.n_fft, params.hop_size, 0
         p.window_kind, p.window_param = params.window.kind, params.window.param
-        self._cw = None
-        if params.window.kind == _ffi.WIN_CUSTOM:
-            self._cw = np.ascontiguousarray(params.window.coefficients, np.float64)
-            p.custom_window = self._cw.ctypes.data_as(C.POINTER(C.c_double))
-            p.custom_window_len = self._cw.size
+        self._cw, p.custom_window, p.custom_window_len = _ffi.custom_window(params.window)
         p.sample_rate_hz = params.sample_rate
         p.freq_scale, p.amp_scale = _ffi.FREQ_LINEAR, _ffi.AMP_COMPLEX
         p.dtype, p.device = self._dt, _ffi.DEVICE_CURRENT if device is None else int(device)
@@ -93,11 +89,8 @@ class WelchPlan(_ffi.NativeHandle):
         st = self._lib.sgx_welch_create(C.byref(p), _KINDS[kind], _DETRENDS[params.detrend], _SCALINGS[params.scaling], _ROUTES[route],
                                         0 if max_scratch_bytes is None else int(max_scratch_bytes), C.byref(h))
         self._create(st, h)
-        self._device = int(self._lib.sgx_welch_device(h))
         self.n_bins = int(self._lib.sgx_welch_n_bins(h))
 
-    device = property(lambda self: self._device)
-    dtype = property(lambda self: "float32" if self._dt == _ffi.F32 else "float64")
     kernel_name = property(lambda self: self._lib.sgx_welch_kernel_name(self._h).decode(), doc='"k_welch" or "welch_generic"')
     tile = property(lambda self: int(self._lib.sgx_welch_tile(self._h)), doc="segments per workgroup tile of k_welch; 0 on the generic route")
     scale = property(lambda self: float(self._lib.sgx_welch_scale(self._h)), doc="1 / (sample_rate sum w^2) or 1 / (sum w)^2, in f64")
@@ -134,88 +127,51 @@ class WelchPlan(_ffi.NativeHandle):
     def compute(self, x, y=None) -> np.ndarray:
         """(n,) or (batch, n) -> (n_bins,) or (batch, n_bins); complex for kind "csd"."""
         self._pair_check(y)
-        a = np.ascontiguousarray(x, dtype=self._np)
-        if a.ndim not in (1, 2):
-            raise ValueError("x must be 1-D (n,) or 2-D (batch, n)")
-        xb = a[None] if a.ndim == 1 else a
-        if xb.shape[0] == 0:
-            raise ValueError("batch must be > 0")
+        xb, squeezed = self._host_rows(x, "x (n,)")
         yb = None
         if y is not None:
-            yb = np.ascontiguousarray(y, dtype=self._np)
-            if yb.shape != a.shape:
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: x has shape {a.shape}, y {yb.shape}", expected=a.size, got=yb.size)
+            if np.shape(y) != np.shape(x):
+                raise _ffi.DimensionMismatchError(f"Dimension mismatch: x has shape {np.shape(x)}, y {np.shape(y)}",
+                                                  expected=xb.size, got=int(np.prod(np.shape(y))))
+            yb, _ = self._host_rows(y, "y (n,)")
         b, n = xb.shape
         cplx = self.kind == "csd"
         out = np.empty((b, self.n_bins * (2 if cplx else 1)), self._np)
         self._check(self._lib.sgx_welch_execute(self._h, xb.ctypes.data, None if yb is None else yb.ctypes.data, b, n, n, out.ctypes.data,
                                                 out.size, _ffi.MEM_HOST, None))
         if cplx:
-            out = out.view(np.complex64 if self._dt == _ffi.F32 else np.complex128)
-        return out[0] if a.ndim == 1 else out
+            out = out.view(self._cdt)
+        return out[0] if squeezed else out
 
     # ---- device tensors (torch), on the current stream --------------------------------------------------------------------
-    def _rows(self, t, what):
-        """-> the row stride in elements.  Rows may be a slice `X[:, a:b]` of a resident tensor (unit inner stride)."""
-        if not t.is_cuda or t.device.index != self._device:
-            raise ValueError(f"{what} is on {t.device}, the plan is bound to cuda:{self._device}")
-        if t.dim() != 2 or t.shape[0] == 0:
-            raise ValueError(f"{what} must be 2-D with batch > 0, got shape {tuple(t.shape)}")
-        b, n = t.shape
-        stride = t.stride(0) if b > 1 else max(n, 1)
-        if t.dtype != self._tdt or not (t.is_contiguous() or ((n <= 1 or t.stride(1) == 1) and stride >= n)):
-            raise ValueError(f"{what} must be a tensor of the plan's dtype, contiguous or with unit inner stride")
-        return stride
-
     def compute_torch(self, x, y=None, out=None):
-        """(batch, n) device tensors -> (batch, n_bins) (complex for kind "csd"), asynchronous on the current stream."""
-        import torch
+        """(batch, n) device tensors -> (batch, n_bins) (complex for kind "csd"), asynchronous on the current stream.  Rows may be a
+        slice `X[:, a:b]` of a resident tensor (unit inner stride)."""
         self._pair_check(y)
-        stride = self._rows(x, "x")
+        stride = self._check_tensor(x, "x", 2, rows_may_stride=True)
         b, n = x.shape
         if y is not None:
             if tuple(y.shape) != tuple(x.shape):
                 raise _ffi.DimensionMismatchError(f"Dimension mismatch: x has shape {tuple(x.shape)}, y {tuple(y.shape)}")
-            if self._rows(y, "y") != stride:
+            if self._check_tensor(y, "y", 2, rows_may_stride=True) != stride:
                 raise ValueError("x and y must have the same row stride")
         cplx = self.kind == "csd"
-        odt = self._tdt if not cplx else (torch.complex64 if self._dt == _ffi.F32 else torch.complex128)
-        if out is None:
-            out = torch.empty((b, self.n_bins), dtype=odt, device=x.device)
-        else:
-            if not out.is_cuda or out.device != x.device or out.dtype != odt or not out.is_contiguous():
-                raise ValueError("out must be a contiguous tensor of the result's dtype on the plan's device")
-            if tuple(out.shape) != (b, self.n_bins):
-                raise _ffi.DimensionMismatchError(f"Dimension mismatch: expected {(b, self.n_bins)}, got {tuple(out.shape)}")
-        s = torch.cuda.current_stream(x.device).cuda_stream
+        out = self._out_tensor(out, (b, self.n_bins), x.device, self._tcdt if cplx else None)
         self._check(self._lib.sgx_welch_execute(self._h, x.data_ptr(), None if y is None else y.data_ptr(), b, n, stride, out.data_ptr(),
-                                                out.numel() * (2 if cplx else 1), _ffi.MEM_DEVICE, C.c_void_p(s)))
+                                                out.numel() * (2 if cplx else 1), _ffi.MEM_DEVICE, self._stream()))
         return out
 
 
 # ---- one-shot functions with a plan cache (cleared by clear_fft_plan_cache) ---------------------------------------------------
-_WELCH_CACHE = {}
-_WELCH_CACHE_MAX = 16
+_WELCH_CACHE = _ffi.PlanCache()
 
 
 def _plan(params, kind, dtype) -> WelchPlan:
     from .functions import _key
-    import torch
     if not isinstance(params, WelchParams):
         raise TypeError("params must be a WelchParams")
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    key = (_key(params), kind, parse_dtype(dtype), dev)
-    plan = _WELCH_CACHE.pop(key, None)
-    if plan is None:
-        plan = WelchPlan(params, kind, dtype)
-        while len(_WELCH_CACHE) >= _WELCH_CACHE_MAX:
-            _WELCH_CACHE.pop(next(iter(_WELCH_CACHE)))
-    _WELCH_CACHE[key] = plan  # most recently used last
-    return plan
-
-
-def clear_welch_plan_cache() -> None:
-    _WELCH_CACHE.clear()
+    key = (_key(params), kind, parse_dtype(dtype), _ffi.current_device_key())
+    return _WELCH_CACHE.get(key, lambda: WelchPlan(params, kind, dtype))
 
 
 def welch(x, params: WelchParams, dtype: str = "float64"):

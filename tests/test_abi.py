@@ -32,6 +32,52 @@ def test_library_exports_every_declared_symbol():
     assert _ffi.lib().sgx_abi_version() == 7
 
 
+_C_SCALARS = {"size_t": C.c_size_t, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "double": C.c_double,
+              "float": C.c_float}
+_C_RETURNS = {"sgx_status": C.c_int, "void": None, "const char *": C.c_char_p, "size_t": C.c_size_t, "int32_t": C.c_int32,
+              "double": C.c_double}
+
+
+def _header_declarations():
+    """{name: (return type, [parameter types])} of every function include/spectro_hip.h declares, as C text without the names; a
+    pointer of any kind is "*"."""
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "spectro_hip.h")).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^(sgx_status|void|size_t|int32_t|double|const char \*)\s*(sgx_\w+)\s*\(([^;{}()]*)\)\s*;", hdr, re.M):
+        types = []
+        for prm in (q.strip() for q in params.split(",")):
+            if prm == "void" and "," not in params:
+                continue
+            m = re.fullmatch(r"(?:const\s+)?(\w+)\s+(\**)\s*(?:const\s+)?\w+", prm)
+            assert m, (name, prm)
+            types.append("*" if m.group(2) else m.group(1))
+        assert name not in out, name
+        out[name] = (ret, types)
+    return out
+
+
+def test_signature_table_matches_every_header_declaration():
+    """Every function the header declares has one entry in _ffi.SIGNATURES with the header's parameter count, a ctypes class per
+    parameter that has the C type's width and kind, and the header's return type: an entry that is missing or shorter would let ctypes
+    pass a size_t or a pointer as a C int."""
+    decl = _header_declarations()
+    assert set(decl) == set(_ffi.SIGNATURES), set(decl) ^ set(_ffi.SIGNATURES)  # (the parser sees every declaration: none is listed by hand)
+    for name, (ret, types) in decl.items():
+        restype, argtypes = _ffi.SIGNATURES[name]
+        assert restype is _C_RETURNS[ret], (name, ret, restype)
+        assert len(argtypes) == len(types), (name, types, argtypes)
+        for i, (ctype, arg) in enumerate(zip(types, argtypes)):
+            if ctype == "*":
+                assert arg in (C.c_void_p, C.c_char_p) or issubclass(arg, C._Pointer), (name, i, arg)
+            else:
+                assert arg is _C_SCALARS[ctype], (name, i, ctype, arg)
+    # and lib() has applied the table to the loaded library
+    L = _ffi.lib()
+    for name, (restype, argtypes) in _ffi.SIGNATURES.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == list(argtypes), name
+
+
 def test_params_struct_layout_matches_header():
     # field order / types of sgx_params as declared in the header
     hdr = open(os.path.join(ROOT, "include", "spectro_hip.h")).read()

@@ -760,7 +760,8 @@ def test_every_stream_taking_prototype_of_the_new_families_has_a_stream_test():
     for name, test in STREAM_COVERAGE.items():
         fn = globals()[test]
         assert any(mark.name == "gpu" for mark in getattr(fn, "pytestmark", [])), test
-    # the Python layer hands every one of them torch's current stream
+    # the Python layer hands every one of them torch's current stream (through the stream helper of the plans' shared base, which fetches it)
     src = open(os.path.join(os.path.dirname(_ffi.__file__), "fir.py")).read()
+    base = open(os.path.join(os.path.dirname(_ffi.__file__), "_handle.py")).read()
     for name in STREAM_COVERAGE:
-        assert name in src and "current_stream" in src
+        assert name in src and "self._stream()" in src and "current_stream" in base

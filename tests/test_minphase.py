@@ -640,7 +640,8 @@ def test_every_stream_taking_prototype_of_the_family_has_a_stream_test():
         for test in tests:
             fn = globals()[test]
             assert any(mark.name == "gpu" for mark in getattr(fn, "pytestmark", [])), test
-    # the Python layer hands it torch's current stream
+    # the Python layer hands it torch's current stream (through the stream helper of the plans' shared base, which fetches it)
     src = open(os.path.join(os.path.dirname(_ffi.__file__), "minphase.py")).read()
+    base = open(os.path.join(os.path.dirname(_ffi.__file__), "_handle.py")).read()
     for name in STREAM_COVERAGE:
-        assert name in src and "current_stream" in src
+        assert name in src and "self._stream()" in src and "current_stream" in base
