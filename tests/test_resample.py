@@ -71,9 +71,9 @@ def host_plan(orig, new, dtype=F64, **kw):
 
 
 @functools.lru_cache(maxsize=None)
-def geometry(orig, new, dtype):
-    """(M, L, K, j0, T-valued table as f64, tile of the tuned route or 1024 where the ratio has none)."""
-    p = host_plan(orig, new, dtype)
+def geometry(orig, new, dtype, **kw):
+    """(M, L, K, j0, T-valued table as f64, tile of the tuned route or 1024 where the ratio has none); `kw`: the filter keywords."""
+    p = host_plan(orig, new, dtype, **kw)
     return p.down, p.up, p.taps_per_phase, p.phase_offsets(), p.taps(), p.tile or 1024
 
 
