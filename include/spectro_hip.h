@@ -823,6 +823,86 @@ const char *sgx_welch_kernel_name(const sgx_welch *plan); /* "k_welch" or "welch
 int32_t sgx_welch_device(const sgx_welch *plan);
 const char *sgx_welch_last_error(const sgx_welch *plan); /* NULL plan: the text of the last failed create */
 
+/* ---- Kaldi plans: batched Kaldi-compatible filterbank (fbank) and MFCC features of whole signals, with the semantics of
+ * torchaudio.compliance.kaldi.fbank / .mfcc for dither = 0 and vtln_warp = 1, one row per batch item.  sgx_params cannot express them:
+ * a frame shorter than the transform, per-frame mean removal and pre-emphasis before the window, triangles on Kaldi's mel scale, the
+ * natural log and a frames x features layout.
+ *   sizes     N = int(fs frame_length_ms / 1000) (window_size), shift = int(fs frame_shift_ms / 1000) (window_shift), P = the next power
+ *             of two >= N with round_to_power_of_two, else N (padded_window_size)
+ *   frames    snip_edges != 0: m = 1 + (n - N) / shift, frame t starts at t shift.  snip_edges == 0: m = (n + shift / 2) / shift, frame t
+ *             starts at t shift + shift / 2 - N / 2 and the row is mirrored at both ends: index i < 0 reads x[-i - 1], i >= n reads
+ *             x[2 n - 1 - i].  n < N is SGX_DIM_MISMATCH in both modes (torchaudio returns an empty matrix)
+ *   per frame 1. remove_dc_offset: subtract the frame's mean;  2. raw_energy: the log energy, log(max(sum f^2, eps_T)), then
+ *             max(., log(energy_floor)) when energy_floor > 0;  3. preemphasis_coefficient a != 0: f[j] - a f[j - 1] with f[-1] := f[0];
+ *             4. the window;  5. the log energy here when raw_energy == 0;  6. zero-pad to P, real FFT;  7. |X|, squared with use_power.
+ *             The mean leaves the samples before the difference and the window; it is not folded into a later term
+ *   windows   with a = 2 pi / (N - 1): hanning 0.5 - 0.5 cos(a j); hamming 0.54 - 0.46 cos(a j); povey hanning^0.85; rectangular;
+ *             blackman c - 0.5 cos(a j) + (0.5 - c) cos(2 a j), c = blackman_coeff
+ *   bank      num_mel_bins x (P / 2 + 1), the last column (Nyquist) zero; high_freq <= 0 means high_freq + fs / 2;
+ *             mel(f) = 1127 ln(1 + f / 700); band b has left, centre, right at mel(low) + (b, b + 1, b + 2) delta,
+ *             delta = (mel(high) - mel(low)) / (bins + 1); the weight at bin k < P / 2 is
+ *             max(0, min((mel(k fs / P) - l) / (c - l), (r - mel(k fs / P)) / (r - c)))
+ *   fbank     E = spectrum . bank^T; with use_log_fbank log(max(E, eps_T)); eps_T = 2^-23 (f32) or 2^-52 (f64).  use_energy adds the
+ *             log energy as a column: first, or last with htk_compat.  n_out = num_mel_bins (+ 1)
+ *   MFCC      num_ceps > 0: the log-power fbank (use_power and use_log_fbank are not read) times the first num_ceps rows of the
+ *             orthonormal DCT-II, D[i][b] = s_i sqrt(2 / B) cos(pi / B (b + 1/2) i), s_0 = 1 / sqrt 2, times the lifter
+ *             1 + Q / 2 sin(pi i / Q) when Q = cepstral_lifter != 0; use_energy replaces C0 with the log energy, htk_compat moves C0
+ *             to the last column.  n_out = num_ceps
+ *   subtract_mean  subtracts each column's mean over the row's frames
+ *   out       [batch][m][n_out] T: frames x features, as Kaldi lays them out
+ * Every maximum keeps a NaN: a frame that holds a non-finite sample is non-finite in every feature and no other frame is.
+ * The tables are built in extended precision on the host, rounded once to f64 (the accessors below) and cast to T; torchaudio builds
+ * them in f32.
+ * Routes: "k_kaldi" (SGX_KALDI_ROUTE_AUTO, P = 256, 512, 1024 or 2048 and at most 256 bands): one fused launch — a workgroup takes a
+ * tile of sgx_kaldi_tile consecutive frames of one row, preprocesses and transforms them on chip and stores nothing but the features;
+ * "kaldi_generic" (every other P up to 2^20, and any P with SGX_KALDI_ROUTE_GENERIC): frames gathered to scratch, transformed by an
+ * internal plan, then bank, log, DCT and energy, over chunks of at most max_scratch_bytes per buffer (0: 256 MiB).  subtract_mean is
+ * one more small launch that adds a row's frames in frame order.  No route uses atomics: a row's result is the same bits whatever the
+ * batch size, the row's place in the batch, the number of calls and, on the generic route, the chunk size.
+ * Rows: row r at x + r * sample_stride (elements of T, sample_stride >= n_samples); out_elems must be batch * m * n_out else
+ * SGX_DIM_MISMATCH; mem_kind as sgx_execute, `stream` a hipStream_t as its hip_stream.
+ * Not offered (SGX_INVALID_INPUT, the text names the field): dither != 0, vtln_warp != 1, spectrogram != 0 (kaldi.spectrogram, a plan
+ * without a bank), min_duration != 0, streaming != 0 (push / flush; the features are frame-local, so they can move onto the streaming
+ * stage later).  Other errors (SGX_INVALID_INPUT), after torchaudio's asserts: N < 2, shift < 1, P > 2^20, low_freq outside
+ * [0, fs / 2), high_freq outside (0, fs / 2], low_freq >= high_freq, preemphasis_coefficient outside [0, 1], num_ceps > num_mel_bins,
+ * num_mel_bins <= 3 (or above 8192), an unknown window_type, dtype or route.  device -1: the current device, -2: a host-only plan (every
+ * accessor below; execute and reserve return SGX_BACKEND behind their shape checks). */
+typedef struct sgx_kaldi sgx_kaldi; /* opaque; same single-caller rule as sgx_fir */
+enum { SGX_KALDI_WIN_HANNING = 0, SGX_KALDI_WIN_HAMMING = 1, SGX_KALDI_WIN_POVEY = 2, SGX_KALDI_WIN_RECTANGULAR = 3, SGX_KALDI_WIN_BLACKMAN = 4 };
+enum { SGX_KALDI_ROUTE_AUTO = 0, SGX_KALDI_ROUTE_GENERIC = 1 };
+typedef struct sgx_kaldi_params {
+    double sample_frequency, frame_length_ms, frame_shift_ms;
+    double blackman_coeff, preemphasis_coefficient, energy_floor, low_freq, high_freq;
+    double dither, vtln_warp, min_duration, cepstral_lifter;
+    int32_t window_type, remove_dc_offset, raw_energy, round_to_power_of_two, snip_edges;
+    int32_t use_energy, use_power, use_log_fbank, htk_compat, subtract_mean;
+    int32_t spectrogram, streaming; /* must be 0 */
+    uint32_t num_mel_bins, num_ceps; /* num_ceps 0: fbank */
+    int32_t dtype, device;
+} sgx_kaldi_params;
+sgx_status sgx_kaldi_create(const sgx_kaldi_params *params, int32_t route, size_t max_scratch_bytes, sgx_kaldi **out);
+void sgx_kaldi_destroy(sgx_kaldi *plan);
+size_t sgx_kaldi_window_size(const sgx_kaldi *plan);        /* N */
+size_t sgx_kaldi_window_shift(const sgx_kaldi *plan);       /* shift */
+size_t sgx_kaldi_padded_window_size(const sgx_kaldi *plan); /* P */
+size_t sgx_kaldi_n_out(const sgx_kaldi *plan);              /* features per frame */
+size_t sgx_kaldi_n_frames(const sgx_kaldi *plan, size_t n_samples); /* m; 0 when n_samples < N */
+sgx_status sgx_kaldi_window(const sgx_kaldi *plan, double *window /* [N] */);
+sgx_status sgx_kaldi_mel_banks(const sgx_kaldi *plan, double *banks /* dense [num_mel_bins][P / 2 + 1] */);
+sgx_status sgx_kaldi_dct(const sgx_kaldi *plan, double *dct /* [num_ceps][num_mel_bins] */);
+sgx_status sgx_kaldi_lifter(const sgx_kaldi *plan, double *lifter /* [num_ceps] */);
+sgx_status sgx_kaldi_execute(sgx_kaldi *plan, const void *x, size_t batch, size_t n_samples, size_t sample_stride, void *out, size_t out_elems,
+                             int32_t mem_kind, void *stream);
+/* Pre-sizes the generic route's chunk scratch and the internal plan's and, with host_staging, the SGX_MEM_HOST staging for calls of up
+ * to `batch` rows of n_samples samples, so that those calls do not allocate. */
+sgx_status sgx_kaldi_reserve(sgx_kaldi *plan, size_t batch, size_t n_samples, int32_t host_staging);
+/* A diagnostic: how many times the plan has allocated or replaced one of its own buffers. */
+size_t sgx_kaldi_allocations(const sgx_kaldi *plan);
+size_t sgx_kaldi_tile(const sgx_kaldi *plan);             /* frames per workgroup tile of "k_kaldi"; 0 on the generic route */
+const char *sgx_kaldi_kernel_name(const sgx_kaldi *plan); /* "k_kaldi" or "kaldi_generic" */
+int32_t sgx_kaldi_device(const sgx_kaldi *plan);
+const char *sgx_kaldi_last_error(const sgx_kaldi *plan); /* NULL plan: the text of the last failed create */
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db
                         fft_plan_cache_info)
 from .gammatone import GammatonePlan, gammatone_center_frequencies, gammatone_iir_spectrogram
 from .fir import DeconvPlan, FirPlan, OverlapSaveConvolver, fft_convolve, fft_deconvolve
+from .kaldi import KaldiParams, KaldiPlan, kaldi_fbank, kaldi_mfcc
 from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .minphase import MinPhasePlan, minimum_phase, minimum_phase_with
 from .params import (ChromaNorm, ChromaParams, CqtParams, ErbParams, GammatoneParams, LogHzParams, LogParams, MelNorm, MelParams,
@@ -69,4 +70,5 @@ __all__ = [
     "cqt", "CqtResult", "CqtTransformPlan", "GammatoneSource", "CqtSource", "ChromaSource", "MfccSource",
     "StreamingPlan", "StreamingInversePlan", "ResamplePlan", "resample",
     "WelchParams", "WelchPlan", "welch", "csd", "coherence",
+    "KaldiParams", "KaldiPlan", "kaldi_fbank", "kaldi_mfcc",
 ]

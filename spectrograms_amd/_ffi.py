@@ -30,6 +30,8 @@ WELCH_PSD, WELCH_CSD, WELCH_COHERENCE = 0, 1, 2
 WELCH_DETREND_NONE, WELCH_DETREND_CONSTANT, WELCH_DETREND_LINEAR = 0, 1, 2
 WELCH_DENSITY, WELCH_SPECTRUM = 0, 1
 WELCH_ROUTE_AUTO, WELCH_ROUTE_GENERIC = 0, 1
+KALDI_WIN_HANNING, KALDI_WIN_HAMMING, KALDI_WIN_POVEY, KALDI_WIN_RECTANGULAR, KALDI_WIN_BLACKMAN = range(5)
+KALDI_ROUTE_AUTO, KALDI_ROUTE_GENERIC = 0, 1
 
 class SgxParams(C.Structure):
     _fields_ = [
@@ -56,6 +58,19 @@ BINAURAL_ITD, BINAURAL_IPD, BINAURAL_ILD, BINAURAL_ILR = range(4)
 class SgxBinauralParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("start_freq", C.c_double), ("end_freq", C.c_double), ("magphase_power", C.c_uint32),
                 ("wrapped", C.c_int32)]
+
+
+class SgxKaldiParams(C.Structure):
+    _fields_ = [
+        ("sample_frequency", C.c_double), ("frame_length_ms", C.c_double), ("frame_shift_ms", C.c_double),
+        ("blackman_coeff", C.c_double), ("preemphasis_coefficient", C.c_double), ("energy_floor", C.c_double), ("low_freq", C.c_double),
+        ("high_freq", C.c_double), ("dither", C.c_double), ("vtln_warp", C.c_double), ("min_duration", C.c_double),
+        ("cepstral_lifter", C.c_double),
+        ("window_type", C.c_int32), ("remove_dc_offset", C.c_int32), ("raw_energy", C.c_int32), ("round_to_power_of_two", C.c_int32),
+        ("snip_edges", C.c_int32), ("use_energy", C.c_int32), ("use_power", C.c_int32), ("use_log_fbank", C.c_int32),
+        ("htk_compat", C.c_int32), ("subtract_mean", C.c_int32), ("spectrogram", C.c_int32), ("streaming", C.c_int32),
+        ("num_mel_bins", C.c_uint32), ("num_ceps", C.c_uint32), ("dtype", C.c_int32), ("device", C.c_int32),
+    ]
 
 
 # ---- the C ABI, once: name -> (restype, argtypes), grouped by family as include/spectro_hip.h is.  lib() applies it; tests/test_abi.py
@@ -210,6 +225,16 @@ SIGNATURES = {
     "sgx_welch_scale": (_f64, [_vp]),
     "sgx_welch_execute": (_ST, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _i32, _vp]),
     "sgx_welch_reserve": (_ST, _RESERVE),
+    # Kaldi fbank / MFCC features (sgx_kaldi)
+    "sgx_kaldi_create": (_ST, [_P(SgxKaldiParams), _i32, _sz, _P(_vp)]),
+    **_family("sgx_kaldi", sizes=("window_size", "window_shift", "padded_window_size", "n_out", "tile", "allocations")),
+    "sgx_kaldi_n_frames": (_sz, [_vp, _sz]),
+    "sgx_kaldi_window": (_ST, [_vp, _P(_f64)]),
+    "sgx_kaldi_mel_banks": (_ST, [_vp, _P(_f64)]),
+    "sgx_kaldi_dct": (_ST, [_vp, _P(_f64)]),
+    "sgx_kaldi_lifter": (_ST, [_vp, _P(_f64)]),
+    "sgx_kaldi_execute": (_ST, _EXEC),
+    "sgx_kaldi_reserve": (_ST, _RESERVE),
 }
 SYMBOLS = list(SIGNATURES)  # every symbol include/spectro_hip.h declares
 
