@@ -32,7 +32,7 @@
  *    frames): sgx_reserve sizes it ahead; a call that fits what was reserved
  *    allocates nothing, a larger one grows the scratch once.
  *  - Streams (the batched 1-D entry points: sgx_execute, sgx_istft, sgx_mdct_forward / _inverse, sgx_binaural_execute /
- *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush, sgx_resample_resample / _process / _flush / _reset, sgx_welch_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
+ *    _histogram, sgx_gammatone_execute, sgx_fir_process / _convolve / _reset, sgx_deconv_execute, sgx_minphase_execute, sgx_stream_push / _flush, sgx_istream_push / _flush, sgx_resample_resample / _process / _flush / _reset, sgx_welch_execute, sgx_kaldi_execute): a device-pointer call enqueues ALL of its work on `hip_stream` — every launch of a
  *    multi-launch route, the memsets in front of the inverse kernels, every chunk of a long batch — and on nothing else, and
  *    returns without waiting for it: to the caller it is one operation of that stream, ordered behind what was queued there
  *    before and in front of what is queued there afterwards.  A plan's scratch belongs to one in-flight call at a time: calls
@@ -43,8 +43,8 @@
  *    the plan's history, sgx_stream_push the stream's pending samples, sgx_istream_push the stream's overlap tail, sgx_resample_process the rows' last K - 1 samples, in stream order).  A device-pointer call that fits what was reserved (host_staging = 0 suffices) allocates nothing, does
  *    not synchronise and copies nothing from the host, so it can be captured into a hipGraph, as a linear chain, and replayed;
  *    a call that has to grow scratch frees and allocates, which waits for the device and cannot be captured.  Pinned per route
- *    by tests/test_stream_order.py (sgx_stream_push / _flush: tests/test_streaming.py; sgx_istream_push / _flush:
- *    tests/test_streaming_inverse.py; the sgx_resample calls: tests/test_resample.py; sgx_welch_execute: tests/test_welch.py).
+ *    by tests/test_stream_order.py, the state-carrying calls as fixed schedules (push, push, flush; reset, process, process, flush)
+ *    on one plan; the sgx_fir calls and sgx_deconv_execute by tests/test_fir.py, sgx_minphase_execute by tests/test_minphase.py.
  */
 #ifndef SPECTRO_HIP_H
 #define SPECTRO_HIP_H

@@ -36,7 +36,8 @@
 //   resample_generic      every other table (and any ratio when asked for): k_resample_generic<T>, one work item per output, table
 //                         [L][K] and samples from global memory.  L K above kMaxTable = 2^22 entries is SGX_INVALID_INPUT.
 // Streaming: the device holds each row's last K - 1 samples in the first of two plan-owned buffers; k_resample_hist writes the next
-// history into the second and it is copied back on the stream, so no launch reads what it writes (as k_fir_hist).  The host holds N
+// history into the second and k_resample_hist_set copies it back on the stream, so no launch reads what it writes (as k_fir_hist);
+// reset and flush zero the first buffer with the same kernel, so a streaming call enqueues launches only.  The host holds N
 // (samples consumed) and E (outputs emitted); window starts rise with m, so after a push E = #{m : floor(m / L) M + j0(m mod L) + K - 1
 // <= N - 1} is a prefix of the outputs and the first output still owed starts no earlier than N - (K - 1).
 #include <algorithm>
@@ -221,6 +222,13 @@ __global__ __launch_bounds__(256) void k_resample_hist(const T *x, u64 sample_st
         const i64 m = (i64)n - (i64)H + j;
         hout[i] = m >= 0 ? x[b * sample_stride + (u64)m] : hin[b * H + (u64)((i64)H + m)];
     }
+}
+
+// the first history buffer from the second (src) or as zeros (src == nullptr).  A launch, not hipMemcpyAsync / hipMemsetAsync: a
+// streaming call is then a chain of kernels only, which a captured graph replays in order
+template <typename T>
+__global__ __launch_bounds__(256) void k_resample_hist_set(T *h, const T *src, u64 total) {
+    for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < total; i += (u64)gridDim.x * 256u) h[i] = src ? src[i] : T(0);
 }
 
 unsigned grid_for(u64 total) {
@@ -409,6 +417,19 @@ sgx_status hist_reserve(sgx_resample *p, size_t rows, hipStream_t s) {
     return SGX_OK;
 }
 
+// the first `elems` elements of d_hist[0]: those of d_hist[1] (from_next) or zeros, as one launch on s
+hipError_t hist_set(sgx_resample *p, bool from_next, size_t elems, hipStream_t s) {
+    if (elems == 0) return hipSuccess;
+    const dim3 grid(grid_for(elems));
+    if (p->dtype == SGX_F64)
+        hipLaunchKernelGGL(k_resample_hist_set<double>, grid, dim3(256), 0, s, p->d_hist[0].as<double>(),
+                           from_next ? (const double *)p->d_hist[1].as<double>() : nullptr, (u64)elems);
+    else
+        hipLaunchKernelGGL(k_resample_hist_set<float>, grid, dim3(256), 0, s, p->d_hist[0].as<float>(),
+                           from_next ? (const float *)p->d_hist[1].as<float>() : nullptr, (u64)elems);
+    return hipGetLastError();
+}
+
 enum Mode { WHOLE, PUSH, FLUSH };
 
 // the three compute calls behind their argument checks; the state moves only when everything went out
@@ -451,9 +472,9 @@ sgx_status rs_call(sgx_resample *p, Mode mode, const void *x, size_t batch, size
             hipLaunchKernelGGL(k_resample_hist<float>, dim3(grid), dim3(256), 0, s, (const float *)dx, (u64)dstride, (u64)n,
                                p->d_hist[0].as<float>(), p->d_hist[1].as<float>(), unsigned(H), unsigned(batch));
         SGX_TRY_HIP(p, hipGetLastError());
-        SGX_TRY_HIP(p, hipMemcpyAsync(p->d_hist[0], p->d_hist[1], batch * H * p->elem, hipMemcpyDeviceToDevice, s));
+        SGX_TRY_HIP(p, hist_set(p, true, batch * H, s));
     }
-    if (mode == FLUSH && H && p->d_hist[0].ptr) SGX_TRY_HIP(p, hipMemsetAsync(p->d_hist[0], 0, p->d_hist[0].bytes, s));
+    if (mode == FLUSH && H && p->d_hist[0].ptr) SGX_TRY_HIP(p, hist_set(p, false, p->d_hist[0].bytes / p->elem, s));
     if (mem_kind == SGX_MEM_HOST) {
         if (n_out) SGX_TRY_HIP(p, hipMemcpyAsync(out, p->d_out, out_elems * p->elem, hipMemcpyDeviceToHost, s));
         SGX_TRY_HIP(p, hipStreamSynchronize(s));
@@ -561,7 +582,7 @@ sgx_status sgx_resample_reset(sgx_resample *p, void *stream) {
     if (p->device == -2 || !p->d_hist[0].ptr) return SGX_OK;
     DeviceGuard dg;
     SGX_TRY_HIP(p, dg.enter(p->device));
-    SGX_TRY_HIP(p, hipMemsetAsync(p->d_hist[0], 0, p->d_hist[0].bytes, static_cast<hipStream_t>(stream)));
+    SGX_TRY_HIP(p, hist_set(p, false, p->d_hist[0].bytes / p->elem, static_cast<hipStream_t>(stream)));
     return SGX_OK;
 }
 
