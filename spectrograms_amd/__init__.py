@@ -24,6 +24,8 @@ from .functions import (clear_fft_plan_cache, compute_chromagram, compute_cqt_db
                         fft_plan_cache_info)
 from .gammatone import GammatonePlan, gammatone_center_frequencies, gammatone_iir_spectrogram
 from .fir import DeconvPlan, FirPlan, OverlapSaveConvolver, fft_convolve, fft_deconvolve
+from .iir import (IirPlan, allpass_biquad, bandpass_biquad, bandreject_biquad, biquad, deemphasis_sos, equalizer_biquad, highpass_biquad,
+                  lowpass_biquad, preemphasis_sos, sosfilt, sosfilt_zi, sosfiltfilt)
 from .kaldi import KaldiParams, KaldiPlan, kaldi_fbank, kaldi_mfcc
 from .mdct import MdctParams, MdctPlan, imdct, mdct
 from .minphase import MinPhasePlan, minimum_phase, minimum_phase_with
@@ -71,4 +73,6 @@ __all__ = [
     "StreamingPlan", "StreamingInversePlan", "ResamplePlan", "resample",
     "WelchParams", "WelchPlan", "welch", "csd", "coherence",
     "KaldiParams", "KaldiPlan", "kaldi_fbank", "kaldi_mfcc",
+    "IirPlan", "sosfilt", "sosfiltfilt", "sosfilt_zi", "biquad", "lowpass_biquad", "highpass_biquad", "bandpass_biquad",
+    "bandreject_biquad", "allpass_biquad", "equalizer_biquad", "preemphasis_sos", "deemphasis_sos",
 ]

@@ -32,6 +32,7 @@ WELCH_DENSITY, WELCH_SPECTRUM = 0, 1
 WELCH_ROUTE_AUTO, WELCH_ROUTE_GENERIC = 0, 1
 KALDI_WIN_HANNING, KALDI_WIN_HAMMING, KALDI_WIN_POVEY, KALDI_WIN_RECTANGULAR, KALDI_WIN_BLACKMAN = range(5)
 KALDI_ROUTE_AUTO, KALDI_ROUTE_GENERIC = 0, 1
+IIR_ROUTE_AUTO, IIR_ROUTE_SPLIT, IIR_ROUTE_CHAIN = 0, 1, 2
 
 class SgxParams(C.Structure):
     _fields_ = [
@@ -238,6 +239,22 @@ SIGNATURES = {
 }
 SYMBOLS = list(SIGNATURES)  # every symbol include/spectro_hip.h declares
 
+# the IIR family's block, a table of its own because its declarations live in include/spectro_hip_iir.h; lib() applies it after SIGNATURES
+# and tests/test_iir.py checks it against that header by the rules of tests/test_abi.py
+IIR_SIGNATURES = {
+    "sgx_iir_create": (_ST, [_P(_f64), _sz, _sz, _i32, _i32, _i32, _P(_vp)]),
+    **_family("sgx_iir", sizes=("n_sections", "padlen", "tile", "block", "allocations")),
+    "sgx_iir_filter": (_ST, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _i32, _vp]),
+    "sgx_iir_process": (_ST, _EXEC),
+    "sgx_iir_filtfilt": (_ST, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _i64, _i32, _vp]),
+    "sgx_iir_reset": (_ST, [_vp, _vp]),
+    "sgx_iir_state": (_ST, [_vp, _P(_f64), _sz, _vp]),
+    "sgx_iir_set_state": (_ST, [_vp, _P(_f64), _sz, _vp]),
+    "sgx_iir_reserve": (_ST, _RESERVE),
+    "sgx_iir_transition": (_ST, [_vp, _i32, _P(_f64)]),
+    "sgx_iir_zi": (_ST, [_vp, _P(_f64)]),
+}
+
 
 class SpectrogramError(Exception):
     """Base error (src/python/error.rs:10-66)."""
@@ -284,7 +301,7 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **IIR_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L

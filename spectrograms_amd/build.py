@@ -19,7 +19,7 @@ LIB = os.path.join(PKG, "libspectro_hip.so")
 OBJ = os.path.join(ROOT, "build", "obj")
 # the single source list (Makefile and tools/ read it through `python -m spectrograms_amd.build --sources`)
 SOURCES = ["plan.hip", "fft2d.hip", "shard.hip", "kernels_generic.hip", "kernels_r32x16.hip", "kernels_r32x32.hip", "kernels_istft2048.hip", "kernels_d32x16.hip", "kernels_istft_d1024.hip", "kernels_r64x32.hip", "kernels_d32x32.hip", "kernels_fft2d.hip",
-           "kernels_c2c1024.hip", "kernels_reg2d.hip", "membench.hip", "bluestein.hip", "bigfft.hip", "cqt.hip", "mdct.hip", "binaural.hip", "gammatone.hip", "fir.hip", "minphase.hip", "stream.hip", "istream.hip", "resample.hip", "welch.hip", "kaldi.hip"]
+           "kernels_c2c1024.hip", "kernels_reg2d.hip", "membench.hip", "bluestein.hip", "bigfft.hip", "cqt.hip", "mdct.hip", "binaural.hip", "gammatone.hip", "fir.hip", "minphase.hip", "stream.hip", "istream.hip", "resample.hip", "welch.hip", "kaldi.hip", "iir.hip"]
 ARCH = "gfx950"
 LINK_LIBS = ["-ldl"]
 
@@ -37,7 +37,7 @@ def _cflags() -> list[str]:
 
 def _headers_mtime() -> float:
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hs.append(os.path.join(ROOT, "include", "spectro_hip.h"))
+    hs += [os.path.join(ROOT, "include", h) for h in ("spectro_hip.h", "spectro_hip_iir.h")]
     return max(os.path.getmtime(h) for h in hs)
 
 
@@ -56,7 +56,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", "spectro_hip.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("spectro_hip.h", "spectro_hip_iir.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
