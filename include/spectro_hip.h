@@ -359,6 +359,10 @@ const char *sgx_last_create_error(void);
  * (the frames' samples staged in LDS) or "cqt_mfma_global" (spans too large for LDS) (a diagnostic: a call may step down this chain for
  * shapes the plan's kernel does not take). */
 const char *sgx_kernel_name(const sgx_plan *plan);
+/* Kernel of the plan's last successful sgx_execute / sgx_execute_timed call, "" before any: one of sgx_kernel_name's names, after the
+ * call's own steps down the chain (a signal past a shape-specific kernel's 32-bit offsets runs on "reg_radix", a row past that kernel's on
+ * "lds_radix2" / "two_factor_dft" / "direct_dft").  A diagnostic; a call in chunks reports its last chunk. */
+const char *sgx_execute_kernel_name(const sgx_plan *plan);
 /* Route of the plan's last successful sgx_istft / sgx_c2r call, "" before any: the fused inverse STFT kernels "istft1024c",
  * "istft2048", "istft_d512", "istft_d1024", "istft_reg", or rows into a frame scratch then the overlap-add, "c2r_reg+ola",
  * "c2r_chirpz+ola", "c2r_chirpz_half+ola", "c2r_rows+ola", "big+ola"; sgx_c2r: the same rows without "+ola". */

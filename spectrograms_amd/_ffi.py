@@ -119,6 +119,7 @@ SIGNATURES = {
     "sgx_last_error": (_str, [_vp]),
     "sgx_last_create_error": (_str, []),
     "sgx_kernel_name": (_str, [_vp]),
+    "sgx_execute_kernel_name": (_str, [_vp]),
     "sgx_istft_kernel_name": (_str, [_vp]),
     "sgx_bank_stage_name": (_str, [_vp]),
     "sgx_abi_version": (_i32, []),

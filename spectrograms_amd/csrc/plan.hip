@@ -557,6 +557,14 @@ const TunedKernel *tuned_kernel(KernelKind k) {
     return nullptr;
 }
 bool kind_is_tuned(KernelKind k) { return tuned_kernel(k) != nullptr; }
+// sgx_kernel_name's text for `kind` on this plan: the kind a call resolved to (sgx_execute_kernel_name)
+const char *kernel_name_of(sgx_plan *pl, KernelKind kind) {
+    const KernelKind planned = pl->kind;
+    pl->kind = kind;
+    const char *name = sgx_kernel_name(pl);
+    pl->kind = planned;
+    return name;
+}
 
 // tw1, tw2 and the half window of a plan on tuned kernel `k` (the layouts: beside kTuned)
 template <typename T>
@@ -1099,7 +1107,11 @@ sgx_status run_cqt(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, 
 
 sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_samples, size_t stride, void *out,
                       size_t n_frames, hipStream_t s, int iters, float *ms) {
-    if (pl->kind == K_CQT) return run_cqt(pl, x, batch, n_samples, stride, out, n_frames, s, iters, ms);
+    if (pl->kind == K_CQT) {
+        const sgx_status st = run_cqt(pl, x, batch, n_samples, stride, out, n_frames, s, iters, ms);
+        if (st == SGX_OK) pl->exec_route = kernel_name_of(pl, K_CQT);
+        return st;
+    }
     StftArgs a;
     void *stage_out = out;
     bool mfcc = pl->p.n_mfcc > 0;
@@ -1157,6 +1169,7 @@ sgx_status run_device(sgx_plan *pl, const void *x, size_t batch, size_t n_sample
     if (st != SGX_OK) return st;
     pl->bank_stage = t_bank_stage;  // (string literals: the name is put together when it is asked for)
     pl->bank_epilogue = t_bank_epilogue;
+    pl->exec_route = kernel_name_of(pl, kind);  // (the first launch's kernel: a call may have stepped down the chain from pl->kind)
     return SGX_OK;
 }
 
@@ -1495,6 +1508,8 @@ const char *sgx_kernel_name(const sgx_plan *plan) {
     default: return "direct_dft";
     }
 }
+
+const char *sgx_execute_kernel_name(const sgx_plan *plan) { return plan ? plan->exec_route : ""; }
 
 sgx_status sgx_plan_create(const sgx_params *params, sgx_plan **out) {
     if (out) *out = nullptr;

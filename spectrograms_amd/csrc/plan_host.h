@@ -80,6 +80,7 @@ struct sgx_plan {
     const char *bank_stage = "", *bank_epilogue = "";  // filterbank stage (+ MFCC launch) of the last successful execute (sgx_bank_stage_name): "" before any / without a bank
     mutable std::string bank_stage_text;               // the two put together for the caller
     const char *istft_route = "";  // route of the last successful sgx_istft / sgx_c2r (sgx_istft_kernel_name): "" before any
+    const char *exec_route = "";   // kernel of the last successful forward launch, after the chain (sgx_execute_kernel_name): "" before any
     // K_BIGFFT: tables of the global-memory transforms and their sequence scratch (grown on demand, pre-sized by sgx_reserve)
     sgx::BigDev big;
     unsigned big_n = 0;  // set at creation when the plan's kind is K_BIGFFT (host-only plans have no tables)

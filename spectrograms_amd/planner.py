@@ -285,6 +285,11 @@ class Plan:
         return self._lib.sgx_kernel_name(self._h).decode()
 
     @property
+    def execute_kernel_name(self) -> str:
+        """Kernel of the last successful compute call (sgx_execute_kernel_name), after its steps down the chain; "" before any."""
+        return self._lib.sgx_execute_kernel_name(self._h).decode()
+
+    @property
     def istft_kernel_name(self) -> str:
         """Route of the last successful istft_batch / istft / c2r call (sgx_istft_kernel_name); "" before any."""
         return self._lib.sgx_istft_kernel_name(self._h).decode()
