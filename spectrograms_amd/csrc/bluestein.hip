@@ -110,7 +110,6 @@ template <typename T, int A_, int B_, int C_>
 __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_fused(BsFused a, unsigned ltile) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, N = A * BC, HA = A / 2;
-    constexpr int LA = ct_log2_ceil(A), LB = ct_log2_ceil(B);
     static_assert(ct_is_pow2(N) && A % 2 == 0, "k_bs_fused: power-of-two convolution lengths");
     typedef RrLayout<sizeof(V), A_, B_, C_> L;
     constexpr unsigned RS = L::RS, FS = L::FS;
@@ -141,7 +140,6 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_fused(B
     const T *x = (const T *)a.x;
     const V *wc = (const V *)a.wc, *chirp = (const V *)a.chirp, *bhp = (const V *)a.bhp, *tw = (const V *)a.tw;
     const unsigned n = a.n;
-    auto wrap = [](unsigned e) { return e & (N - 1); };
     auto item = [&](unsigned idx, unsigned &s, unsigned &r) {
         r = idx % BC;
         s = idx / BC;
@@ -195,15 +193,7 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_fused(B
                 v[n1] = inreg::cmulv(p[q][n1], w[q][n1]);  // (xa + i xb) wc
                 v[n1 + HA] = (V){T(0), T(0)};
             }
-            inreg::MixFft<A, V>::run(v);
-            V pw2[LA];
-#pragma unroll
-            for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-            V *dst = buf + (size_t)s * FS;
-            const unsigned pp = L::hi_part(r / C) ^ (r % C);
-            dst[pp ^ L::k1_mask(0)] = v[0];
-#pragma unroll
-            for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ L::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
+            rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
         }
     }
     BS_STAMP(1);
@@ -215,16 +205,10 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_fused(B
         V ch[HA];
 #pragma unroll
         for (unsigned n1 = 0; n1 < HA; ++n1) ch[n1] = n1 * BC + r < n ? chirp[n1 * BC + r] : (V){T(0), T(0)};
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
         V *dst = buf + (size_t)s * FS;
         const unsigned pp = L::hi_part(r / C) ^ (r % C);
         V v[A];
-        v[0] = dst[pp ^ L::k1_mask(0)];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) v[k1] = inreg::cmulv((dst + (pp ^ L::k1_mask(k1)))[k1 * RS], rr_twiddle<LA>(pw2, k1));
-        inreg::MixFft<A, V>::run(v);
+        rr_pass1_load<T, A_, B_, C_>(v, dst, r, tw);
 #pragma unroll
         for (unsigned n1 = 0; n1 < HA; ++n1) {
             const V y = {v[n1].x, -v[n1].y};
@@ -367,7 +351,6 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_c2c(BsC
     constexpr bool HERM = RMODE == 1, HALF = RMODE == 2, FWDH = RMODE == 3;  // 0: complex sequences
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, N = A * BC, HA = A / 2;
-    constexpr int LA = ct_log2_ceil(A);
     typedef RrLayout<sizeof(V), A_, B_, C_> L;
     constexpr unsigned RS = L::RS, FS = L::FS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -384,7 +367,6 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_c2c(BsC
     const V *chirp = (const V *)a.chirp, *bhp = (const V *)a.bhp, *tw = (const V *)a.tw;
     const unsigned n = a.n, half = n / 2;
     const T cj = (RMODE == 0 && a.inverse) ? T(-1) : T(1);  // inverse = conj(forward(conj x)); HERM is an inverse by construction (below)
-    auto wrap = [](unsigned e) { return e & (N - 1); };
     auto item = [&](unsigned idx, unsigned &s, unsigned &r) {
         if (a.in_seq_fast) { s = idx & (tile - 1); r = idx >> ltile; } else { r = idx % BC; s = idx / BC; }
         return idx < tile * BC && s < ns;
@@ -455,15 +437,7 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_c2c(BsC
                 v[n1 + HA] = (V){T(0), T(0)};
             }
         }
-        inreg::MixFft<A, V>::run(v);
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-        V *dst = buf + (size_t)s * FS;
-        const unsigned pp = L::hi_part(r / C) ^ (r % C);
-        dst[pp ^ L::k1_mask(0)] = v[0];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ L::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
+        rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
     }
     bs_middle<T, A_, B_, C_>(buf, ns, tid, tw, bhp BS_STAMP_ARGS);
     for (unsigned idx = tid; idx < tile * BC; idx += 256) {
@@ -472,16 +446,10 @@ __global__ __launch_bounds__(256, (bs_waves<T, A_, B_, C_>())) void k_bs_c2c(BsC
         V ch[HA];
 #pragma unroll
         for (unsigned n1 = 0; n1 < HA; ++n1) ch[n1] = n1 * BC + r < n ? chirp[n1 * BC + r] : (V){T(0), T(0)};
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
         V *dst = buf + (size_t)s * FS;
         const unsigned pp = L::hi_part(r / C) ^ (r % C);
         V v[A];
-        v[0] = dst[pp ^ L::k1_mask(0)];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) v[k1] = inreg::cmulv((dst + (pp ^ L::k1_mask(k1)))[k1 * RS], rr_twiddle<LA>(pw2, k1));
-        inreg::MixFft<A, V>::run(v);
+        rr_pass1_load<T, A_, B_, C_>(v, dst, r, tw);
 #pragma unroll
         for (unsigned n1 = 0; n1 < HA; ++n1) {
             const V y = {v[n1].x, -v[n1].y};
@@ -565,7 +533,7 @@ bool fused_geometry(unsigned M, int dtype, unsigned &fa, unsigned &fb, unsigned 
     if (M & (M - 1)) return false;
     if (!bs_split(M, dtype, fa, fb, fc)) return false;
     const size_t es = dtype == SGX_F64 ? 8 : 4;
-    const size_t fs = rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs);
+    const size_t fs = rr_seq_elems(2 * (unsigned)es, fa, fb, fc);
     const size_t budget = bs_lds_budget(dtype, M);
     ltile = 4;  // up to 16 pairs = 32 frames per workgroup
     while (ltile > 0 && (size_t)(1u << ltile) * fs * 2 * es > budget) --ltile;
@@ -635,7 +603,7 @@ hipError_t run_bsc(BsC2c f, int herm, unsigned M, unsigned batch, int dtype, hip
     if (!fused_geometry(M, dtype, fa, fb, fc, ltile, lds)) return hipErrorNotSupported;
     ltile = std::min(ltile + 1u, 5u);  // (fused_geometry caps at 16 frame pairs; sequences: up to 32, no more than the job has)
     const size_t es = dtype == SGX_F64 ? 8 : 4;
-    const size_t fs = rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs);
+    const size_t fs = rr_seq_elems(2 * (unsigned)es, fa, fb, fc);
     while (ltile > 0 && ((size_t)(1u << ltile) * fs * 2 * es > bs_lds_budget(dtype, M) || (1u << (ltile - 1)) >= f.nseq)) --ltile;
     lds = (size_t)(1u << ltile) * fs * 2 * es;
     f.tiles = (f.nseq + (1u << ltile) - 1) >> ltile;

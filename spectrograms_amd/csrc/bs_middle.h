@@ -1,9 +1,11 @@
 // bs_middle.h — the middle of an in-LDS circular convolution on the register-tiled passes, shared by the chirp-z kernels
 // (bluestein.hip) and the overlap-save FIR kernel (fir.hip): forward passes 2 and 3, the product with a plan table taken where
 // pass 3 leaves the bins, and the same passes run back (the derivation is at k_bs_fused).
+// Its pass 2 shares a loop with the two-pass product and its back pass 2 is the only one of its kind, so both stay written out
+// here instead of going through rr_pass2 (rr_passes.h): with rr_pass2 inside bs_middle k_fir_os<float, 16, 16, 8> went from 124
+// to 146 registers (profiles/rr_passes_codegen.txt).  Pass 1 and its inverse around bs_middle are rr_pass1_store / rr_pass1_load.
 #pragma once
-#include "reg_radix.h"
-#include "rr_layout.h"
+#include "rr_passes.h"
 
 namespace sgx {
 
@@ -35,7 +37,6 @@ __device__ __forceinline__ void bs_middle(typename PairOf<T>::type *buf, unsigne
     constexpr int LB = ct_log2_ceil(B);
     typedef RrLayout<sizeof(V), A_, B_, C_> L;
     constexpr unsigned RS = L::RS, FS = L::FS;
-    auto wrap = [](unsigned e) { return e & (N - 1); };
     __syncthreads();
     BS_STAMP(2);
     // P2 (+ T2); two-pass splits: P2, product, P2^-1
@@ -50,7 +51,7 @@ __device__ __forceinline__ void bs_middle(typename PairOf<T>::type *buf, unsigne
         if constexpr (C > 1) {
             V q2[LB];
 #pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
+            for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<N>((A << j) * n3)];
             row[lp ^ L::hi_part(0)] = v[0];
 #pragma unroll
             for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = inreg::cmulv(v[k2], rr_twiddle<LB>(q2, k2));
@@ -99,7 +100,7 @@ __device__ __forceinline__ void bs_middle(typename PairOf<T>::type *buf, unsigne
             const unsigned lp = n3 ^ L::k1_mask(k1);
             V q2[LB];
 #pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
+            for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<N>((A << j) * n3)];
             V v[B];
             v[0] = row[lp ^ L::hi_part(0)];
 #pragma unroll

@@ -82,10 +82,9 @@ template <typename T, int A_, int B_, int C_>
 __global__ __launch_bounds__(256, (fir_waves<T, A_, B_, C_>())) void k_fir_os(FirArgs a, unsigned ltile) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, P = A * BC;
-    constexpr int LA = ct_log2_ceil(A);
     static_assert(ct_is_pow2(P), "k_fir_os: power-of-two segment lengths");
     typedef RrLayout<sizeof(V), A_, B_, C_> Lay;
-    constexpr unsigned RS = Lay::RS, FS = Lay::FS;
+    constexpr unsigned FS = Lay::FS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     V *buf = (V *)smem;  // [tile][FS]
     const unsigned tid = threadIdx.x, tile = 1u << ltile;
@@ -99,7 +98,6 @@ __global__ __launch_bounds__(256, (fir_waves<T, A_, B_, C_>())) void k_fir_os(Fi
     T *out = (T *)a.out + (size_t)b * a.n_out;
     const unsigned L = a.L, S = a.S;
     const unsigned long long n = a.n_samples;
-    auto wrap = [](unsigned e) { return e & (P - 1); };
     auto item = [&](unsigned idx, unsigned &s, unsigned &r) {
         r = idx % BC;
         s = idx / BC;
@@ -123,15 +121,7 @@ __global__ __launch_bounds__(256, (fir_waves<T, A_, B_, C_>())) void k_fir_os(Fi
                 v[n1] = (V){fir_sample(x, hist, L, n, m), T(0)};
             }
         }
-        inreg::MixFft<A, V>::run(v);
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-        V *dst = buf + (size_t)s * FS;
-        const unsigned pp = Lay::hi_part(r / C) ^ (r % C);
-        dst[pp ^ Lay::k1_mask(0)] = v[0];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
+        rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
     }
 #ifdef SGX_BS_STAMPS
     unsigned long long st_acc[14] = {0}, st_prev = 0;
@@ -141,16 +131,8 @@ __global__ __launch_bounds__(256, (fir_waves<T, A_, B_, C_>())) void k_fir_os(Fi
     for (unsigned idx = tid; idx < tile * BC; idx += 256) {
         unsigned s, r;
         if (!item(idx, s, r)) continue;
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-        const V *src = buf + (size_t)s * FS;
-        const unsigned pp = Lay::hi_part(r / C) ^ (r % C);
         V v[A];
-        v[0] = src[pp ^ Lay::k1_mask(0)];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) v[k1] = inreg::cmulv((src + (pp ^ Lay::k1_mask(k1)))[k1 * RS], rr_twiddle<LA>(pw2, k1));
-        inreg::MixFft<A, V>::run(v);
+        rr_pass1_load<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
         const unsigned long long o0 = (unsigned long long)(p0 + s) * S;
 #pragma unroll
         for (unsigned n1 = 0; n1 < A; ++n1) {
@@ -280,11 +262,6 @@ __global__ __launch_bounds__(256) void k_deconv_rows(const T *in, T *out, unsign
     }
 }
 
-unsigned grid_for(unsigned long long total) {
-    const unsigned long long g = (total + 255) / 256;
-    return (unsigned)std::max(1ull, std::min(g, 1ull << 20));
-}
-
 size_t next_pow2(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 // FFT_P of a real sequence on the host: iterative radix-2, f64
@@ -350,7 +327,7 @@ size_t generic_len(size_t taps) { return std::max<size_t>(256, next_pow2(2 * tap
 
 size_t fused_lds_budget(int dtype) { return dtype == SGX_F64 ? kFirLds64 : kFirLds32; }
 size_t fused_seq_bytes(const sgx_fir *p) {
-    return (size_t)rr_frame_stride(p->fa, rr_swizzle(2 * (unsigned)p->elem, p->fa, p->fb, p->fc).rs) * 2 * p->elem;
+    return rr_seq_bytes(2 * (unsigned)p->elem, p->fa, p->fb, p->fc);
 }
 
 template <typename T, int A, int B, int C>
@@ -428,7 +405,7 @@ sgx_status run_generic(sgx_fir *p, const FirArgs &a, hipStream_t s) {
     for (size_t q0 = 0; q0 < total; q0 += gc) {
         g.q0 = q0;
         g.gc = std::min(gc, total - q0);
-        const unsigned grid = grid_for(g.gc * p->P);
+        const unsigned grid = grid_for_items(g.gc * p->P);
         c.nseq = unsigned(g.gc);
         c.tiles = c.tile ? unsigned((g.gc + c.tile - 1) / c.tile) : 0;
         g.seq = p->d_seq;
@@ -479,7 +456,7 @@ sgx_status run_dev(sgx_fir *p, const void *x, size_t batch, size_t n_samples, si
         if (st != SGX_OK) return st;
     }
     if (streaming && L) {
-        const unsigned grid = grid_for(batch * L);
+        const unsigned grid = grid_for_items(batch * L);
         if (p->dtype == SGX_F64)
             hipLaunchKernelGGL(k_fir_hist<double>, dim3(grid), dim3(256), 0, s, (const double *)x, stride, n_samples, p->d_hist[0].as<double>(),
                                p->d_hist[1].as<double>(), unsigned(L), unsigned(batch));
@@ -743,8 +720,8 @@ sgx_status sgx_deconv_execute(sgx_deconv *p, const void *numerator, const void *
         num = p->d_in; den = p->d_in2; dst = p->d_out;
     }
     auto rows = [&](const void *in, void *to, size_t nrows, size_t w_in, size_t w_out) {
-        if (p->dtype == SGX_F64) hipLaunchKernelGGL(k_deconv_rows<double>, dim3(grid_for(nrows * w_out)), dim3(256), 0, s, (const double *)in, (double *)to, nrows, w_in, w_out);
-        else hipLaunchKernelGGL(k_deconv_rows<float>, dim3(grid_for(nrows * w_out)), dim3(256), 0, s, (const float *)in, (float *)to, nrows, w_in, w_out);
+        if (p->dtype == SGX_F64) hipLaunchKernelGGL(k_deconv_rows<double>, dim3(grid_for_items(nrows * w_out)), dim3(256), 0, s, (const double *)in, (double *)to, nrows, w_in, w_out);
+        else hipLaunchKernelGGL(k_deconv_rows<float>, dim3(grid_for_items(nrows * w_out)), dim3(256), 0, s, (const float *)in, (float *)to, nrows, w_in, w_out);
         return hipGetLastError();
     };
     // rows zero-padded to n
@@ -756,11 +733,11 @@ sgx_status sgx_deconv_execute(sgx_deconv *p, const void *numerator, const void *
     const unsigned long long total = (unsigned long long)batch * nb, d_stride = den_rows > 1 ? nb : 0;
     if (p->dtype == SGX_F64) {
         hipLaunchKernelGGL(k_deconv_max<double>, dim3(unsigned(den_rows)), dim3(256), 0, s, p->d_dspec.as<inreg::v2d>(), unsigned(nb), p->d_max.as<double>());
-        hipLaunchKernelGGL(k_deconv_quot<double>, dim3(grid_for(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2d>(), p->d_dspec.as<inreg::v2d>(),
+        hipLaunchKernelGGL(k_deconv_quot<double>, dim3(grid_for_items(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2d>(), p->d_dspec.as<inreg::v2d>(),
                            p->d_max.as<double>(), unsigned(nb), unsigned(n), total, d_stride, p->reg);
     } else {
         hipLaunchKernelGGL(k_deconv_max<float>, dim3(unsigned(den_rows)), dim3(256), 0, s, p->d_dspec.as<inreg::v2f>(), unsigned(nb), p->d_max.as<float>());
-        hipLaunchKernelGGL(k_deconv_quot<float>, dim3(grid_for(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2f>(), p->d_dspec.as<inreg::v2f>(),
+        hipLaunchKernelGGL(k_deconv_quot<float>, dim3(grid_for_items(total)), dim3(256), 0, s, p->d_nspec.as<inreg::v2f>(), p->d_dspec.as<inreg::v2f>(),
                            p->d_max.as<float>(), unsigned(nb), unsigned(n), total, d_stride, float(p->reg));
     }
     SGX_TRY_HIP(p, hipGetLastError());

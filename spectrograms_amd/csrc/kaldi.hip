@@ -37,8 +37,7 @@
 #include <string>
 #include <vector>
 
-#include "reg_radix.h"
-#include "rr_layout.h"
+#include "rr_passes.h"
 #include "plan_host.h"
 #include "xcd_map.h"
 
@@ -144,14 +143,13 @@ template <typename T, int A_, int B_, int C_>
 __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_kaldi(KaldiArgs a) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, P = A * BC, HP = P / 2;
-    constexpr int LA = ct_log2_ceil(A), LB = ct_log2_ceil(B);
     constexpr unsigned LAST = C > 1 ? C : B;
     constexpr unsigned Q = C > 1 ? A * B : A;                 // work items of the last pass per frame
     constexpr unsigned W = BC < 64 ? BC : 64, WPS = BC / W;   // lanes of a wave, waves, that hold one frame in pass 1
     constexpr bool kTableTwiddles = sizeof(T) == 8;           // f64: every twiddle read from the table (f32 builds them from LA entries)
     static_assert(ct_is_pow2(P) && 256 % Q == 0 && 256 % BC == 0 && WPS <= 4, "k_kaldi: power-of-two splits of k_fir_os");
     typedef RrLayout<sizeof(V), A_, B_, C_> Lay;
-    constexpr unsigned RS = Lay::RS, FS = Lay::FS;
+    constexpr unsigned FS = Lay::FS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ T red[2][3][4];  // pass 1, frames over several waves: the waves' sums, one slot per reduction, two iterations' worth
     V *buf = (V *)smem;                      // [sub][FS]
@@ -171,7 +169,6 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_kaldi(Kald
     const V *tw = (const V *)a.tw;
     const T alpha = T(a.alpha), cnt = T(a.N);
     const long long n = (long long)a.n_samples;
-    auto wrap = [](unsigned e) { return e & (P - 1); };
     for (unsigned i = tid; i < a.nval; i += 256) bw[i] = ((const T *)a.bval)[i];
     for (unsigned i = tid; i < 3 * a.bins; i += 256) bd[i] = a.band[i];  // (read behind the barriers of the first round)
 
@@ -265,24 +262,14 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_kaldi(Kald
                 if (valid && r == 0) en[sq] = kaldi_log_energy(a, esum);
             }
             if (!valid) continue;
-            inreg::MixFft<A, V>::run(v);
-            V *dst = buf + (size_t)sq * FS;
-            const unsigned pp = Lay::hi_part(r / C) ^ (r % C);
-            dst[pp ^ Lay::k1_mask(0)] = v[0];
-            if constexpr (kTableTwiddles) {  // W^(k1 r) as the table has it: one rounding, against up to LA - 1 products of entries
-#pragma unroll
-                for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], tw[wrap(k1 * r)]);
-            } else {
-                V pw2[LA];
-#pragma unroll
-                for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-#pragma unroll
-                for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
-            }
+            rr_pass1_store<T, A_, B_, C_, kTableTwiddles>(v, buf + (size_t)sq * FS, r, tw);
         }
         __syncthreads();
         if constexpr (C > 1) {
-            // P2 + T2
+            // P2 + T2: this kernel's own copy of rr_pass2 (rr_passes.h).  With the shared loop, and with a per-item helper, the register
+            // allocation of k_kaldi<float, 16, 16, 8> goes from 4 to 6 spilled registers (profiles/rr_passes_codegen.txt).
+            constexpr unsigned RS = Lay::RS;
+            constexpr int LB = ct_log2_ceil(B);
             for (unsigned idx = tid; idx < nq * A * C; idx += 256) {
                 const unsigned sq = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
                 V *row = buf + (size_t)sq * FS + k1 * RS;
@@ -294,11 +281,11 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_kaldi(Kald
                 row[lp ^ Lay::hi_part(0)] = v[0];
                 if constexpr (kTableTwiddles) {
 #pragma unroll
-                    for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], tw[wrap(A * k2 * n3)]);
+                    for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], tw[rr_wrap<P>(A * k2 * n3)]);
                 } else {
                     V q2[LB];
 #pragma unroll
-                    for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
+                    for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<P>((A << j) * n3)];
 #pragma unroll
                     for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], rr_twiddle<LB>(q2, k2));
                 }
@@ -312,10 +299,7 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_kaldi(Kald
             const unsigned k1 = C > 1 ? q / B : q;
             const unsigned lp = (C > 1 ? Lay::hi_part(q % B) : 0u) ^ Lay::k1_mask(k1);
             V vx[LAST];
-            const V *rx = buf + (size_t)s * FS + k1 * RS;
-#pragma unroll
-            for (unsigned j = 0; j < LAST; ++j) vx[j] = rx[lp ^ (C > 1 ? j : Lay::hi_part(j))];
-            inreg::MixFft<LAST, V>::run(vx);
+            rr_last_load<T, A_, B_, C_>(vx, buf + (size_t)s * FS + k1 * Lay::RS, lp);
             T *sp = spec + (size_t)s * HP;
 #pragma unroll
             for (unsigned j = 0; j < LAST; ++j) {
@@ -436,11 +420,6 @@ __global__ __launch_bounds__(256) void k_kaldi_cmn(T *out, unsigned long long m,
     }
 }
 
-unsigned grid_for(unsigned long long total) {
-    const unsigned long long g = (total + 255) / 256;
-    return (unsigned)std::max(1ull, std::min(g, 1ull << 20));
-}
-
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------------
@@ -469,7 +448,7 @@ sgx_status kgrow(sgx_kaldi *p, DevBuf &b, size_t need) {
 }
 
 size_t fused_frame_bytes(const sgx_kaldi *p) {
-    const size_t seq = (size_t)rr_frame_stride(p->fa, rr_swizzle(2 * (unsigned)p->elem, p->fa, p->fb, p->fc).rs) * 2 * p->elem;
+    const size_t seq = rr_seq_bytes(2 * (unsigned)p->elem, p->fa, p->fb, p->fc);
     return seq + (p->P / 2 + p->bins + 1) * p->elem;
 }
 // the workgroup's copy of the bank: its weights and its rows
@@ -486,10 +465,7 @@ hipError_t launch_kaldi_t(const KaldiArgs &a, size_t lds, hipStream_t s) {
 #define SGX_KALDI_SPLITS_F64(X) X(8, 8, 4) X(8, 8, 8) X(16, 8, 8) X(16, 16, 8)
 
 bool fused_split_known(int dtype, unsigned fa, unsigned fb, unsigned fc) {
-#define SGX_KALDI_HAS(A, B, C) if (fa == A && fb == B && fc == C) return true;
-    if (dtype == SGX_F64) { SGX_KALDI_SPLITS_F64(SGX_KALDI_HAS) } else { SGX_KALDI_SPLITS_F32(SGX_KALDI_HAS) }
-#undef SGX_KALDI_HAS
-    return false;
+    return dtype == SGX_F64 ? SGX_RR_SPLIT_IN(SGX_KALDI_SPLITS_F64, fa, fb, fc) : SGX_RR_SPLIT_IN(SGX_KALDI_SPLITS_F32, fa, fb, fc);
 }
 
 hipError_t launch_fused(const sgx_kaldi *p, const KaldiArgs &a, hipStream_t s) {
@@ -575,8 +551,8 @@ sgx_status run_dev(sgx_kaldi *p, const void *x, size_t batch, size_t n_samples, 
     }
     if (kp.subtract_mean) {
         const unsigned long long total = (unsigned long long)batch * p->n_out;
-        if (f64) hipLaunchKernelGGL(k_kaldi_cmn<double>, dim3(grid_for(total)), dim3(256), 0, s, (double *)out, (unsigned long long)m, unsigned(p->n_out), total);
-        else hipLaunchKernelGGL(k_kaldi_cmn<float>, dim3(grid_for(total)), dim3(256), 0, s, (float *)out, (unsigned long long)m, unsigned(p->n_out), total);
+        if (f64) hipLaunchKernelGGL(k_kaldi_cmn<double>, dim3(grid_for_items(total)), dim3(256), 0, s, (double *)out, (unsigned long long)m, unsigned(p->n_out), total);
+        else hipLaunchKernelGGL(k_kaldi_cmn<float>, dim3(grid_for_items(total)), dim3(256), 0, s, (float *)out, (unsigned long long)m, unsigned(p->n_out), total);
         SGX_TRY_HIP(p, hipGetLastError());
     }
     return SGX_OK;

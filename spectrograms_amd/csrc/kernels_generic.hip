@@ -263,6 +263,7 @@ __global__ __launch_bounds__(256) void k_lds_radix2(StftArgs a) {
 // 3-4 barriers per tile instead of log2(m)/2 + 2, and 2-3 LDS round trips per point instead of log2(m)/2 + 1; no
 // in-register transform is longer than 16 points, so f32 stays under 128 VGPRs (4 waves per SIMD).
 // A, B, C: lengths of the in-register passes (products of 2, 3, 5; C = 1: two passes), m = A B C
+// (the passes are written out here, two items per thread and staged; every other kernel takes them from rr_passes.h)
 template <typename T, int A_, int B_, int C_, bool STAGED_>
 __global__ __launch_bounds__(256, (rr_stft_waves<T, A_, B_, C_, STAGED_>())) void k_reg_radix(StftArgs a, unsigned total_tiles, unsigned csr_lds, unsigned band_lds, unsigned rot) {
     typedef typename PairOf<T>::type V;
@@ -1001,7 +1002,7 @@ static size_t reg_radix_csr_bytes(const StftArgs &a, size_t es) {
 
 // LDS bytes of a tile of ft frames with its tables (without the bank)
 static size_t reg_radix_bytes(const StftArgs &a, unsigned ft, unsigned sub, unsigned fa, unsigned fb, unsigned fc, size_t es) {
-    const size_t fs = rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs);
+    const size_t fs = rr_seq_elems(2 * (unsigned)es, fa, fb, fc);
     const size_t m = (size_t)fa * fb * fc;
     const size_t pws = 4 * ((((size_t)a.nb_fft + 3) >> 2) | 1);
     size_t bytes = (ft * fs + m / 2 + 1 + m) * 2 * es;
@@ -1032,7 +1033,7 @@ static bool reg_radix_want_staged(const StftArgs &a, unsigned fa, unsigned fc, s
 static bool reg_radix_stage_ok(const StftArgs &a, unsigned ft, unsigned fa, unsigned fb, unsigned fc, size_t es) {
     const unsigned long long len = (unsigned long long)(ft - 1) * a.hop + a.n_fft, epc = 16 / es;
     const unsigned long long chunks = (len + epc - 1) / epc;
-    const size_t fs = rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs);
+    const size_t fs = rr_seq_elems(2 * (unsigned)es, fa, fb, fc);
     return chunks <= 256ull * rr_stage_rounds(fa * fb * fc, (unsigned)es) && chunks * 16 <= (unsigned long long)ft * fs * 2 * es;
 }
 

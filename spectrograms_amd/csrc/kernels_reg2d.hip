@@ -14,8 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "reg_radix.h"
-#include "rr_layout.h"
+#include "rr_passes.h"
 #include "xcd_map.h"
 
 namespace sgx {
@@ -28,10 +27,8 @@ template <typename T, int A_, int B_, int C_>
 __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2c_reg(C2cArgs a, unsigned ltile) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, N = A * BC;
-    constexpr int LA = ct_log2_ceil(A), LB = ct_log2_ceil(B);
-    constexpr bool P2 = ct_is_pow2(N);
     typedef RrLayout<sizeof(V), A_, B_, C_> L;  // where element (k1, hi C + lo) of a sequence lives in LDS (rr_layout.h)
-    constexpr unsigned RS = L::RS, FS = L::FS;
+    constexpr unsigned FS = L::FS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     V *buf = (V *)smem;  // [tile][FS]
     const unsigned tid = threadIdx.x, tile = 1u << ltile;
@@ -44,7 +41,6 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2c_reg(C2
     V *out = (V *)a.out + (size_t)b * a.out_img;
     const V *tw = (const V *)a.tw;  // W_N^k, N entries
     const T cj = a.inverse ? T(-1) : T(1);  // inverse = conj(forward(conj x))
-    auto wrap = [](unsigned e) { return P2 ? (e & (N - 1)) : (e % N); };
 
     // pass 1, software-pipelined: the loads of work item idx + 256 are in flight while item idx is transformed
     auto item = [&](unsigned idx, unsigned &s, unsigned &r) {
@@ -70,16 +66,13 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2c_reg(C2
         fetch(idx + 256, nxt);
         unsigned s, r;
         if (!item(idx, s, r)) continue;
-        inreg::MixFft<A, V>::run(v);
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
-        V *dst = buf + (size_t)s * FS;
-        const unsigned pp = L::hi_part(r / C) ^ (r % C);
-        dst[pp ^ L::k1_mask(0)] = v[0];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ L::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
+        rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
     }
+    // Passes 2 and 3 stay written out here (they are rr_pass2 / rr_pass3 of rr_passes.h): through the shared loops, and through
+    // per-item helpers, the three-pass instances' register allocation moves (f64 8 x 8 x 8 123 -> 129 .. 131 registers, f32
+    // 16 x 16 x 8 123 -> 127 .. 144), past the 128 that four workgroups per CU need (profiles/rr_passes_codegen.txt).
+    constexpr unsigned RS = L::RS;
+    constexpr int LB = ct_log2_ceil(B);
     __syncthreads();
     for (unsigned idx = tid; idx < ns * A * C; idx += 256) {
         const unsigned s = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2c_reg(C2
         if constexpr (C > 1) {  // W_(BC)^(k2 n3) = W_N^(A k2 n3)
             V q2[LB];
 #pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
+            for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<N>((A << j) * n3)];
 #pragma unroll
             for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = inreg::cmulv(x[k2], rr_twiddle<LB>(q2, k2));
         } else {
@@ -191,10 +184,8 @@ template <typename T, int A_, int B_, int C_, bool OLA>
 __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2r_reg(C2rArgs a, unsigned ltile) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, M = A * BC, CN = 2 * M;
-    constexpr int LA = ct_log2_ceil(A), LB = ct_log2_ceil(B);
-    constexpr bool P2 = ct_is_pow2(M);
     typedef RrLayout<sizeof(V), A_, B_, C_> L;
-    constexpr unsigned RS = L::RS, FS = L::FS;
+    constexpr unsigned FS = L::FS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned tid = threadIdx.x, tile = 1u << ltile;
     V *buf = (V *)smem;                   // [tile][FS]
@@ -209,7 +200,6 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2r_reg(C2
     const V *in = (const V *)a.in + (size_t)b * a.in_img;
     T *out = (T *)a.out + (size_t)b * a.nrows * CN;
     const V *tw = (const V *)a.tw;  // W_CN^k, CN entries
-    auto wrap = [](unsigned e) { return P2 ? (e & (CN - 1)) : (e % CN); };
     // OLA: behind the tile sit the overlap-add's norm table (hop entries) and a copy of the window (CN entries; visible after the
     // barriers of the passes): the walk reads the window four to eight times per output sample
     T *nrm_tab = (T *)(buf + (size_t)tile * FS), *win_lds = nrm_tab + a.hop;
@@ -244,16 +234,11 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2r_reg(C2
             const V Tt = inreg::cmulv(D, (V){w.x, -w.y});
             v[n1] = inreg::pfma(inreg::swp(Tt), (V){T(-1), T(-1)}, S * (V){T(1), T(-1)});
         }
-        inreg::MixFft<A, V>::run(v);
-        V pw2[LA];
-#pragma unroll
-        for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((2u << j) * r)];  // W_m^e = W_CN^(2e)
-        V *dst = buf + (size_t)rr * FS;
-        const unsigned pp = L::hi_part(r / C) ^ (r % C);
-        dst[pp ^ L::k1_mask(0)] = v[0];
-#pragma unroll
-        for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ L::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
+        rr_pass1_store<T, A_, B_, C_, false, 2>(v, buf + (size_t)rr * FS, r, tw);  // W_m^e = W_CN^(2e)
     }
+    // passes 2 and 3 written out, as in k_c2c_reg (the note there)
+    constexpr unsigned RS = L::RS;
+    constexpr int LB = ct_log2_ceil(B);
     __syncthreads();
     for (unsigned idx = tid; idx < tile * A * C; idx += 256) {
         const unsigned rr = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
@@ -267,7 +252,7 @@ __global__ __launch_bounds__(256, (rr_waves<T, A_, B_, C_>())) void k_c2r_reg(C2
         if constexpr (C > 1) {
             V q2[LB];
 #pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((2u * A << j) * n3)];
+            for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<CN>((2u * A << j) * n3)];
 #pragma unroll
             for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = inreg::cmulv(x[k2], rr_twiddle<LB>(q2, k2));
         } else {
@@ -347,7 +332,7 @@ hipError_t launch_c2c_reg(const C2cArgs &a0, int dtype, hipStream_t s) {
     if (kRegOff || !reg_split_len(a0.n, dtype, &fa, &fb, &fc)) return hipErrorNotSupported;
     const size_t es = elem_size(dtype);
     if (((size_t)a0.in | (size_t)a0.out) & (2 * es - 1)) return hipErrorNotSupported;
-    const size_t fs = rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs);
+    const size_t fs = rr_seq_elems(2 * (unsigned)es, fa, fb, fc);
     unsigned ltile = 5;  // up to 32 sequences per workgroup; no more than the job has
     // a quarter of a CU's LDS (four workgroups per CU overlap their phases: 2048 x 512^2 fft2d 1.91 -> 1.74 ms, 8192 x 256^2
     // 1.81 -> 1.63 ms) unless that leaves fewer than 8 sequences per tile (128 x 2048^2: 2.32 ms with 4 per tile, 2.77 with 2)
@@ -386,7 +371,7 @@ static hipError_t c2r_reg_plan(const C2rArgs &a0, int dtype, C2rArgs &a, unsigne
     const size_t es = elem_size(dtype);
     if (((size_t)a0.in | (size_t)a0.out | (size_t)a0.win) & (2 * es - 1)) return hipErrorNotSupported;
     const size_t m = a0.ncols / 2;
-    const size_t per = (size_t)rr_frame_stride(fa, rr_swizzle(2 * (unsigned)es, fa, fb, fc).rs) * 2 * es;
+    const size_t per = rr_seq_bytes(2 * (unsigned)es, fa, fb, fc);
     (void)m;
     const bool ola = a0.hop != 0;  // fused inverse STFT (launch_istft_reg)
 #ifndef SGX_C2R_KB

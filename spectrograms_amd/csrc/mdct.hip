@@ -38,8 +38,7 @@
 #include <string>
 #include <vector>
 
-#include "reg_radix.h"
-#include "rr_layout.h"
+#include "rr_passes.h"
 #include "plan_host.h"
 #include "xcd_map.h"
 
@@ -67,75 +66,6 @@ struct MdctArgs {
 // f32 instances take the 256 registers of that occupancy (the fold of pass 1 holds four samples and four window values per point)
 template <typename T, int A_, int B_, int C_>
 constexpr unsigned mdct_waves() { return rr_waves<T, A_, B_, C_>() < 2 ? rr_waves<T, A_, B_, C_>() : 2; }
-
-// The M-point transform's passes 2 and 3 on `rows` rows of the tile (pass 1 wrote them), as in k_c2c_reg.
-template <typename T, int A_, int B_, int C_>
-__device__ __forceinline__ void mdct_passes23(typename PairOf<T>::type *buf, unsigned rows, const typename PairOf<T>::type *tw, unsigned tid) {
-    typedef typename PairOf<T>::type V;
-    constexpr unsigned A = A_, B = B_, C = C_, M = A * B * C;
-    constexpr int LB = ct_log2_ceil(B);
-    constexpr bool P2 = ct_is_pow2(M);
-    typedef RrLayout<sizeof(V), A_, B_, C_> L;
-    constexpr unsigned RS = L::RS, FS = L::FS;
-    auto wrap = [](unsigned e) { return P2 ? (e & (M - 1)) : (e % M); };
-    __syncthreads();
-    for (unsigned idx = tid; idx < rows * A * C; idx += 256) {
-        const unsigned s = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
-        V *row = buf + (size_t)s * FS + k1 * RS;
-        const unsigned lp = n3 ^ L::k1_mask(k1);
-        V x[B];
-#pragma unroll
-        for (unsigned n2 = 0; n2 < B; ++n2) x[n2] = row[lp ^ L::hi_part(n2)];
-        inreg::MixFft<B, V>::run(x);
-        row[lp ^ L::hi_part(0)] = x[0];
-        if constexpr (C > 1) {
-            V q2[LB];
-#pragma unroll
-            for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
-#pragma unroll
-            for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = inreg::cmulv(x[k2], rr_twiddle<LB>(q2, k2));
-        } else {
-#pragma unroll
-            for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ L::hi_part(k2)] = x[k2];
-        }
-    }
-    __syncthreads();
-    if constexpr (C > 1) {
-        for (unsigned idx = tid; idx < rows * A * B; idx += 256) {
-            const unsigned s = idx / (A * B), q = idx % (A * B), k1 = q / B, k2 = q % B;
-            V *row = buf + (size_t)s * FS + k1 * RS;
-            const unsigned lp = L::hi_part(k2) ^ L::k1_mask(k1);
-            V x[C];
-#pragma unroll
-            for (unsigned n3 = 0; n3 < C; ++n3) x[n3] = row[lp ^ n3];
-            inreg::MixFft<C, V>::run(x);
-#pragma unroll
-            for (unsigned k3 = 0; k3 < C; ++k3) row[lp ^ k3] = x[k3];
-        }
-        __syncthreads();
-    }
-}
-
-// pass 1 of the M-point transform for work item (row s, column r): the A points v[n1] = c[BC n1 + r] are in registers
-template <typename T, int A_, int B_, int C_>
-__device__ __forceinline__ void mdct_pass1_store(typename PairOf<T>::type (&v)[A_], typename PairOf<T>::type *buf, unsigned s, unsigned r,
-                                                 const typename PairOf<T>::type *tw) {
-    typedef typename PairOf<T>::type V;
-    constexpr unsigned A = A_, C = C_, M = A_ * B_ * C_;
-    constexpr int LA = ct_log2_ceil(A);
-    constexpr bool P2 = ct_is_pow2(M);
-    typedef RrLayout<sizeof(V), A_, B_, C_> L;
-    constexpr unsigned RS = L::RS, FS = L::FS;
-    inreg::MixFft<A, V>::run(v);
-    V pw2[LA];
-#pragma unroll
-    for (int j = 0; j < LA; ++j) pw2[j] = tw[P2 ? (((1u << j) * r) & (M - 1)) : (((1u << j) * r) % M)];
-    V *dst = buf + (size_t)s * FS;
-    const unsigned pp = L::hi_part(r / C) ^ (r % C);
-    dst[pp ^ L::k1_mask(0)] = v[0];
-#pragma unroll
-    for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ L::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
-}
 
 template <typename T, int A_, int B_, int C_>
 __global__ __launch_bounds__(256, (mdct_waves<T, A_, B_, C_>())) void k_mdct_fwd(MdctArgs a, unsigned ltile) {
@@ -178,9 +108,9 @@ __global__ __launch_bounds__(256, (mdct_waves<T, A_, B_, C_>())) void k_mdct_fwd
             for (unsigned n1 = 0; n1 < A; ++n1) v[n1] = buf[(size_t)s * FS + BC * n1 + r];
         }
         __syncthreads();
-        if (act) mdct_pass1_store<T, A_, B_, C_>(v, buf, s, r, tw);
+        if (act) rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)s * FS, r, tw);
     }
-    mdct_passes23<T, A_, B_, C_>(buf, nf, tw, tid);
+    rr_passes23<T, A_, B_, C_>(buf, nf, tid, tw);
     // post-twiddle; lanes over frames: coefficient row j takes the tile's nf frames in one run of stores
     T *out = (T *)a.out + (size_t)b * N * a.n_frames + f0;
 #pragma unroll 1
@@ -225,9 +155,9 @@ __global__ __launch_bounds__(256, (mdct_waves<T, A_, B_, C_>())) void k_imdct_ol
             const V c = ok ? (V){cf[(size_t)(2u * n) * a.n_frames], cf[(size_t)(N - 1u - 2u * n) * a.n_frames]} : (V){T(0), T(0)};
             v[n1] = inreg::cmulv(c, t1[n]);
         }
-        mdct_pass1_store<T, A_, B_, C_>(v, buf, rr, r, tw);
+        rr_pass1_store<T, A_, B_, C_>(v, buf + (size_t)rr * FS, r, tw);
     }
-    mdct_passes23<T, A_, B_, C_>(buf, tile, tw, tid);
+    rr_passes23<T, A_, B_, C_>(buf, tile, tid, tw);
     // frame sample m of row rr: y[m] = U[m + h] (unfolded DCT-IV, 2/N in t2)
     auto y = [&](unsigned rr, unsigned m) {
         const unsigned p = m + h;
@@ -269,7 +199,7 @@ hipError_t launch_fused_t(const MdctArgs &a, bool inverse, unsigned ltile, size_
 size_t fused_frame_bytes(unsigned M, int dtype, unsigned *fa, unsigned *fb, unsigned *fc) {
     if (!reg_split_len(M, dtype, fa, fb, fc)) return 0;
     const size_t es = elem_size(dtype);
-    return (size_t)rr_frame_stride(*fa, rr_swizzle(2 * (unsigned)es, *fa, *fb, *fc).rs) * 2 * es;
+    return rr_seq_bytes(2 * (unsigned)es, *fa, *fb, *fc);
 }
 
 // log2 of the fused kernels' frames per tile: the largest power of two up to 32 within kMdctLds; -1: not fused.  The forward tile
@@ -461,11 +391,6 @@ __global__ __launch_bounds__(256) void k_mdct_ola(GenArgs a, unsigned long long 
     }
 }
 
-unsigned grid_for(unsigned long long total) {
-    const unsigned long long g = (total + 255) / 256;
-    return (unsigned)std::max(1ull, std::min(g, 1ull << 20));
-}
-
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------------
@@ -544,8 +469,8 @@ sgx_status run_generic(sgx_mdct *p, const void *in, size_t batch, size_t n_sampl
         a.gc = std::min(z.gc, total - g0);
         const unsigned long long nseq = a.gc * (odd ? 2u : 1u);
         const unsigned long long fold_total = nseq * p->L;
-        if (f64) hipLaunchKernelGGL(k_mdct_fold<double>, dim3(grid_for(fold_total)), dim3(256), 0, s, a, int(inverse));
-        else hipLaunchKernelGGL(k_mdct_fold<float>, dim3(grid_for(fold_total)), dim3(256), 0, s, a, int(inverse));
+        if (f64) hipLaunchKernelGGL(k_mdct_fold<double>, dim3(grid_for_items(fold_total)), dim3(256), 0, s, a, int(inverse));
+        else hipLaunchKernelGGL(k_mdct_fold<float>, dim3(grid_for_items(fold_total)), dim3(256), 0, s, a, int(inverse));
         SGX_TRY_HIP(p, hipGetLastError());
         if (!a.direct) {
             C2cArgs c{};
@@ -565,13 +490,13 @@ sgx_status run_generic(sgx_mdct *p, const void *in, size_t batch, size_t n_sampl
             SGX_TRY_HIP(p, e);
         }
         const unsigned long long post_total = a.gc * (inverse ? 2ull * p->n : p->n);
-        if (f64) hipLaunchKernelGGL(k_mdct_post<double>, dim3(grid_for(post_total)), dim3(256), 0, s, a, int(inverse));
-        else hipLaunchKernelGGL(k_mdct_post<float>, dim3(grid_for(post_total)), dim3(256), 0, s, a, int(inverse));
+        if (f64) hipLaunchKernelGGL(k_mdct_post<double>, dim3(grid_for_items(post_total)), dim3(256), 0, s, a, int(inverse));
+        else hipLaunchKernelGGL(k_mdct_post<float>, dim3(grid_for_items(post_total)), dim3(256), 0, s, a, int(inverse));
         SGX_TRY_HIP(p, hipGetLastError());
         if (inverse) {
             const unsigned long long b0 = g0 / n_frames, b1 = (g0 + a.gc - 1) / n_frames, nsig = b1 - b0 + 1;
-            if (f64) hipLaunchKernelGGL(k_mdct_ola<double>, dim3(grid_for(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
-            else hipLaunchKernelGGL(k_mdct_ola<float>, dim3(grid_for(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
+            if (f64) hipLaunchKernelGGL(k_mdct_ola<double>, dim3(grid_for_items(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
+            else hipLaunchKernelGGL(k_mdct_ola<float>, dim3(grid_for_items(nsig * a.out_len)), dim3(256), 0, s, a, b0, nsig);
             SGX_TRY_HIP(p, hipGetLastError());
         }
     }

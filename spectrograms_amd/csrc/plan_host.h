@@ -110,6 +110,13 @@ constexpr const char *kNoDeviceText = "hip -- FFT backend error: plan has no HIP
 
 inline size_t elem_size(int dtype) { return dtype == SGX_F64 ? 8 : 4; }
 
+// Workgroups of a grid-stride kernel over `total` items: 256 threads each, at most 2^20 of them (the kernels walk the rest).
+// (stream.hip / istream.hip cap theirs at 2048 workgroups: a different rule, kept there as grid_for.)
+inline unsigned grid_for_items(unsigned long long total) {
+    const unsigned long long g = (total + 255) / 256, cap = 1ull << 20;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
 // The per-thread text of plan type P's last failed create; <prefix>_last_error(NULL) reads it.
 template <typename P>
 std::string &create_err() {

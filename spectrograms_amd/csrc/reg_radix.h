@@ -145,4 +145,8 @@ inline bool reg_split_len(unsigned len, int dtype, unsigned *pa, unsigned *pb, u
     X(20, 16, 1) X(25, 16, 1) X(24, 20, 1) X(25, 20, 1) X(25, 24, 1) X(30, 24, 1) X(32, 25, 1) X(32, 30, 1)       \
     X(25, 40, 1) X(30, 40, 1) X(32, 40, 1) X(16, 40, 1) X(30, 36, 1)
 
+// whether (a, b, c) is an entry of an X-macro split list (the plan families' own lists included)
+#define SGX_RR_SPLIT_EQ(A, B, C) || (sa_ == A && sb_ == B && sc_ == C)
+#define SGX_RR_SPLIT_IN(LIST, a, b, c) ([](unsigned sa_, unsigned sb_, unsigned sc_) { return false LIST(SGX_RR_SPLIT_EQ); }(a, b, c))
+
 }  // namespace sgx

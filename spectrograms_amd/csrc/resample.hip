@@ -231,11 +231,6 @@ __global__ __launch_bounds__(256) void k_resample_hist_set(T *h, const T *src, u
     for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < total; i += (u64)gridDim.x * 256u) h[i] = src ? src[i] : T(0);
 }
 
-unsigned grid_for(u64 total) {
-    const u64 g = (total + 255) / 256;
-    return (unsigned)std::max<u64>(1, std::min<u64>(g, 1ull << 20));
-}
-
 // I0 by its power series (all terms positive: relative error of a few ulp for the arguments a Kaiser window takes)
 double bessel_i0(double x) {
     const double h = 0.25 * x * x;
@@ -393,7 +388,7 @@ sgx_status run_dev(sgx_resample *p, const void *x, size_t batch, size_t n, size_
         const unsigned threads = unsigned((p->L * p->G + 63) / 64 * 64);
         SGX_TRY_HIP(p, f64 ? launch_pp_t<double>(p, a, threads, lds, s) : launch_pp_t<float>(p, a, threads, lds, s));
     } else {
-        const unsigned grid = grid_for((u64)batch * n_out);
+        const unsigned grid = grid_for_items((u64)batch * n_out);
         if (f64) hipLaunchKernelGGL(k_resample_generic<double>, dim3(grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_resample_generic<float>, dim3(grid), dim3(256), 0, s, a);
         SGX_TRY_HIP(p, hipGetLastError());
@@ -420,7 +415,7 @@ sgx_status hist_reserve(sgx_resample *p, size_t rows, hipStream_t s) {
 // the first `elems` elements of d_hist[0]: those of d_hist[1] (from_next) or zeros, as one launch on s
 hipError_t hist_set(sgx_resample *p, bool from_next, size_t elems, hipStream_t s) {
     if (elems == 0) return hipSuccess;
-    const dim3 grid(grid_for(elems));
+    const dim3 grid(grid_for_items(elems));
     if (p->dtype == SGX_F64)
         hipLaunchKernelGGL(k_resample_hist_set<double>, grid, dim3(256), 0, s, p->d_hist[0].as<double>(),
                            from_next ? (const double *)p->d_hist[1].as<double>() : nullptr, (u64)elems);
@@ -464,7 +459,7 @@ sgx_status rs_call(sgx_resample *p, Mode mode, const void *x, size_t batch, size
     }
     if ((st = run_dev(p, dx, batch, n, dstride, hist, N0, m0, dout, n_out, s)) != SGX_OK) return st;
     if (mode == PUSH && H) {
-        const unsigned grid = grid_for((u64)batch * H);
+        const unsigned grid = grid_for_items((u64)batch * H);
         if (p->dtype == SGX_F64)
             hipLaunchKernelGGL(k_resample_hist<double>, dim3(grid), dim3(256), 0, s, (const double *)dx, (u64)dstride, (u64)n,
                                p->d_hist[0].as<double>(), p->d_hist[1].as<double>(), unsigned(H), unsigned(batch));

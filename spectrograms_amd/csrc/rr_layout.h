@@ -20,6 +20,7 @@
 // the search).  In the kernels a swizzled access is one XOR of a lane value with a compile-time
 // constant, because the fields do not overlap.  Two-pass splits (C = 1) keep k1 * (B + 1) + p, which is conflict-free.
 #pragma once
+#include <cstddef>
 
 namespace sgx {
 
@@ -108,6 +109,10 @@ constexpr RrSwz rr_swizzle(unsigned elem_bytes, unsigned A, unsigned B, unsigned
         if (e.eb == elem_bytes && e.a == A && e.b == B && e.c == C) return e.z;
     return RrSwz{B * C + 1, 0, 0, 0};
 }
+
+// LDS of one frame / sequence of an (A, B, C) split, in complex elements of `elem_bytes` and in bytes (host-side tile sizing)
+constexpr size_t rr_seq_elems(unsigned elem_bytes, unsigned a, unsigned b, unsigned c) { return rr_frame_stride(a, rr_swizzle(elem_bytes, a, b, c).rs); }
+constexpr size_t rr_seq_bytes(unsigned elem_bytes, unsigned a, unsigned b, unsigned c) { return rr_seq_elems(elem_bytes, a, b, c) * elem_bytes; }
 
 // The layout of one kernel instance.  index = k1 RS + (k1_mask(k1) ^ hi_part(hi) ^ lo): in each pass two of the three terms are
 // lane values built once per work item and the third is a compile-time constant of the unrolled loop.

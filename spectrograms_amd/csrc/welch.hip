@@ -33,8 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "reg_radix.h"
-#include "rr_layout.h"
+#include "rr_passes.h"
 #include "plan_host.h"
 #include "xcd_map.h"
 
@@ -109,7 +108,6 @@ template <typename T, int A_, int B_, int C_, int KIND>
 __global__ __launch_bounds__(256, (welch_waves<T, A_, B_, C_, KIND>())) void k_welch(WelchArgs a) {
     typedef typename PairOf<T>::type V;
     constexpr unsigned A = A_, B = B_, C = C_, BC = B * C, P = A * BC, NB = P / 2 + 1;
-    constexpr int LA = ct_log2_ceil(A), LB = ct_log2_ceil(B);
     constexpr unsigned NCH = KIND == KIND_PSD ? 1 : 2, NACC = welch_nacc(KIND);
     constexpr unsigned LAST = C > 1 ? C : B, NBK = LAST / 2 + 1;  // the last pass's points; those at or below n / 2 are kept
     constexpr unsigned Q = C > 1 ? A * B : A, G = 256 / Q;        // work items of the last pass per sequence; threads per item
@@ -131,7 +129,6 @@ __global__ __launch_bounds__(256, (welch_waves<T, A_, B_, C_, KIND>())) void k_w
     const T *win = (const T *)a.win;
     const V *tw = (const V *)a.tw;
     const T inv_n = T(a.inv_n), inv_sxx = T(a.inv_sxx), ctr = T(0.5) * T(P - 1);
-    auto wrap = [](unsigned e) { return e & (P - 1); };
 
     T acc[NACC * NBK];
 #pragma unroll
@@ -195,24 +192,30 @@ __global__ __launch_bounds__(256, (welch_waves<T, A_, B_, C_, KIND>())) void k_w
             const T *pw = win + r;
 #pragma unroll
             for (unsigned n1 = 0; n1 < A; ++n1) v[n1] = (V){xv[n1] * pw[n1 * BC], T(0)};
+            // Pass 1's transform, twiddles and scatter stay written out here (they are rr_pass1_store of rr_passes.h): through the
+            // helper the compiler contracts two multiply-adds of k_welch<float, 8, 8, 8, KIND_PSD>'s detrending into fmas that it
+            // left as packed multiplies and adds before, and the linear-detrend PSD at n = 512 changes in its last bits.
+            constexpr int LA = ct_log2_ceil(A);
             inreg::MixFft<A, V>::run(v);
             V *dst = buf + (size_t)sq * FS;
             const unsigned pp = Lay::hi_part(r / C) ^ (r % C);
             dst[pp ^ Lay::k1_mask(0)] = v[0];
             if constexpr (kTableTwiddles) {  // W^(k1 r) as the table has it: one rounding, against up to LA - 1 products of entries
 #pragma unroll
-                for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], tw[wrap(k1 * r)]);
+                for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], tw[rr_wrap<P>(k1 * r)]);
             } else {
                 V pw2[LA];
 #pragma unroll
-                for (int j = 0; j < LA; ++j) pw2[j] = tw[wrap((1u << j) * r)];
+                for (int j = 0; j < LA; ++j) pw2[j] = tw[rr_wrap<P>((1u << j) * r)];
 #pragma unroll
                 for (unsigned k1 = 1; k1 < A; ++k1) (dst + (pp ^ Lay::k1_mask(k1)))[k1 * RS] = inreg::cmulv(v[k1], rr_twiddle<LA>(pw2, k1));
             }
         }
         __syncthreads();
         if constexpr (C > 1) {
-            // P2 + T2
+            // P2 + T2: this kernel's own copy of rr_pass2 (rr_passes.h).  With the shared loop k_welch<double, 16, 8, 8, KIND_PSD> goes
+            // from 248 to 258 registers, i.e. from two resident workgroups per CU to one (profiles/rr_passes_codegen.txt).
+            constexpr int LB = ct_log2_ceil(B);
             for (unsigned idx = tid; idx < nq * A * C; idx += 256) {
                 const unsigned sq = idx / (A * C), q = idx % (A * C), k1 = q / C, n3 = q % C;
                 V *row = buf + (size_t)sq * FS + k1 * RS;
@@ -224,11 +227,11 @@ __global__ __launch_bounds__(256, (welch_waves<T, A_, B_, C_, KIND>())) void k_w
                 row[lp ^ Lay::hi_part(0)] = v[0];
                 if constexpr (kTableTwiddles) {
 #pragma unroll
-                    for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], tw[wrap(A * k2 * n3)]);
+                    for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], tw[rr_wrap<P>(A * k2 * n3)]);
                 } else {
                     V q2[LB];
 #pragma unroll
-                    for (int j = 0; j < LB; ++j) q2[j] = tw[wrap((A << j) * n3)];
+                    for (int j = 0; j < LB; ++j) q2[j] = tw[rr_wrap<P>((A << j) * n3)];
 #pragma unroll
                     for (unsigned k2 = 1; k2 < B; ++k2) row[lp ^ Lay::hi_part(k2)] = inreg::cmulv(v[k2], rr_twiddle<LB>(q2, k2));
                 }
@@ -241,17 +244,10 @@ __global__ __launch_bounds__(256, (welch_waves<T, A_, B_, C_, KIND>())) void k_w
             const unsigned s = idx / Q, q = idx % Q;
             const unsigned k1 = C > 1 ? q / B : q;
             const unsigned lp = (C > 1 ? Lay::hi_part(q % B) : 0u) ^ Lay::k1_mask(k1);
-            V vx[LAST], vy[NCH > 1 ? LAST : 1];
-            const V *rx = buf + (size_t)(s * NCH) * FS + k1 * RS;
-#pragma unroll
-            for (unsigned j = 0; j < LAST; ++j) vx[j] = rx[lp ^ (C > 1 ? j : Lay::hi_part(j))];
-            inreg::MixFft<LAST, V>::run(vx);
-            if constexpr (NCH > 1) {
-                const V *ry = rx + FS;
-#pragma unroll
-                for (unsigned j = 0; j < LAST; ++j) vy[j] = ry[lp ^ (C > 1 ? j : Lay::hi_part(j))];
-                inreg::MixFft<LAST, V>::run(vy);
-            }
+            V vx[LAST], vy[LAST];  // (vy: LAST entries also where NCH == 1 leaves it unused, to bind to rr_last_load's array reference)
+            const V *rx = buf + (size_t)(s * NCH) * FS + k1 * Lay::RS;
+            rr_last_load<T, A_, B_, C_>(vx, rx, lp);
+            if constexpr (NCH > 1) rr_last_load<T, A_, B_, C_>(vy, rx + FS, lp);
 #pragma unroll
             for (unsigned j = 0; j < NBK; ++j) {
                 if constexpr (NCH > 1) welch_add<KIND, T, V>(acc + j, NBK, vx[j], vy[j]);
@@ -385,11 +381,6 @@ __global__ __launch_bounds__(256) void k_welch_accum(const typename PairOf<T>::t
     }
 }
 
-unsigned grid_for(unsigned long long total) {
-    const unsigned long long g = (total + 255) / 256;
-    return (unsigned)std::max(1ull, std::min(g, 1ull << 20));
-}
-
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------------
@@ -421,7 +412,7 @@ sgx_status wgrow(sgx_welch *p, DevBuf &b, size_t need) {
 }
 
 size_t fused_seq_bytes(const sgx_welch *p) {
-    return (size_t)rr_frame_stride(p->fa, rr_swizzle(2 * (unsigned)p->elem, p->fa, p->fb, p->fc).rs) * 2 * p->elem;
+    return rr_seq_bytes(2 * (unsigned)p->elem, p->fa, p->fb, p->fc);
 }
 
 template <typename T, int A, int B, int C, int KIND>
@@ -446,10 +437,7 @@ hipError_t launch_welch_k(int kind, const WelchArgs &a, size_t lds, hipStream_t 
 #define SGX_WELCH_SPLITS_F64(X) X(8, 8, 4) X(8, 8, 8) X(16, 8, 8) X(16, 16, 8) X(16, 16, 16)
 
 bool fused_split_known(int dtype, unsigned fa, unsigned fb, unsigned fc) {
-#define SGX_WELCH_HAS(A, B, C) if (fa == A && fb == B && fc == C) return true;
-    if (dtype == SGX_F64) { SGX_WELCH_SPLITS_F64(SGX_WELCH_HAS) } else { SGX_WELCH_SPLITS_F32(SGX_WELCH_HAS) }
-#undef SGX_WELCH_HAS
-    return false;
+    return dtype == SGX_F64 ? SGX_RR_SPLIT_IN(SGX_WELCH_SPLITS_F64, fa, fb, fc) : SGX_RR_SPLIT_IN(SGX_WELCH_SPLITS_F32, fa, fb, fc);
 }
 
 hipError_t launch_fused(const sgx_welch *p, const WelchArgs &a, hipStream_t s) {
@@ -488,7 +476,7 @@ sgx_status reserve_dev(sgx_welch *p, size_t batch, size_t m) {
 template <typename T>
 hipError_t launch_fold(const sgx_welch *p, void *out, size_t batch, size_t m, hipStream_t s) {
     const unsigned long long total = (unsigned long long)batch * p->nb;
-    hipLaunchKernelGGL(k_welch_fold<T>, dim3(grid_for(total)), dim3(256), 0, s, p->d_part.as<T>(), (T *)out, unsigned(p->nb),
+    hipLaunchKernelGGL(k_welch_fold<T>, dim3(grid_for_items(total)), dim3(256), 0, s, p->d_part.as<T>(), (T *)out, unsigned(p->nb),
                        unsigned(tiles_of(p, m)), unsigned(p->n), p->kind, p->scale / double(m), total);
     return hipGetLastError();
 }
@@ -497,7 +485,7 @@ template <typename T>
 hipError_t launch_accum(const sgx_welch *p, unsigned long long q0, unsigned long long gc, unsigned long long m, hipStream_t s) {
     typedef typename PairOf<T>::type V;
     const unsigned long long b_lo = q0 / m, b_hi = (q0 + gc - 1) / m, total = (b_hi - b_lo + 1) * p->nb;
-    const dim3 grid(grid_for(total));
+    const dim3 grid(grid_for_items(total));
     if (p->kind == KIND_PSD)
         hipLaunchKernelGGL((k_welch_accum<T, KIND_PSD>), grid, dim3(256), 0, s, p->d_spec.as<V>(), p->d_part.as<T>(), q0, gc, m, unsigned(p->nb), b_lo, total);
     else if (p->kind == KIND_CSD)
