@@ -242,7 +242,7 @@ __device__ __forceinline__ T big_amp(T p, int amp, T eps) {
     if (amp == AMP_DB) {
         const T v = p > eps ? p : eps;
         if constexpr (sizeof(T) == 8) return db_f64(v);
-        else return T(10) * log10(v);
+        else return __builtin_log2f(v) * 3.01029995663981195f;  // as kernels_r32x16.hip
     }
     return p;
 }
